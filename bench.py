@@ -11,6 +11,13 @@ Workload (BASELINE.json configs[1]): per GPU, 1024 chunk files resident in HBM
 Multi-GPU: one process per GPU (torchrun), chunk ranges sharded by rank
 (weak scaling: every rank holds its own 1024 chunks).
 
+A plain run sets the pool up (seeded: the same arguments give the same bytes),
+warms up, times `--steps` steps, writes the last step's outputs if
+`--dump-outputs DIR` is given and prints the line.  Everything else -- the
+verify pass, the read / load-only probes and PMC traffic passes, the digest
+checks, the partial-write, verify-on-read, WAL, CPU-baseline, stream, files and
+scan-op legs -- runs only with `--full`, and adds its keys to the same line.
+
 Prints ONE JSON line on rank 0 (contract in the task statement).
 """
 from __future__ import annotations
@@ -40,6 +47,14 @@ def parse():
     p.add_argument("--warmup", type=int, default=10, help="untimed steps: the first ~7 launches after idle run slow while clocks ramp")
     p.add_argument("--clock-warm-ms", type=float, default=1000.0,
                    help="untimed warm-up floor in ms of estimated work (extra steps beyond --warmup; 0 = none)")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run everything else this file measures or checks: the verify "
+                        "pass, the read and load-only probes, the PMC traffic passes, the digest checks, the "
+                        "partial-write / verify-on-read / WAL legs, the CPU baseline and the host-input legs "
+                        "(the options below choose among them); without it only the headline figure is produced")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last one computed (rank 0's page, metapage, slice and "
+                        "file CRCs and the copyset digests) as DIR/<name>.npy, float64, at most 64 MB in all")
     p.add_argument("--chunks", type=int, default=1024, help="chunks per GPU")
     p.add_argument("--page-bytes", type=int, default=4096)
     p.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU baseline time budget (rank 0, N=1)")
@@ -997,6 +1012,40 @@ def launch_ranks(args):
     sys.exit(subprocess.call(cmd))
 
 
+DUMP_MAX_BYTES = 60_000_000  # --dump-outputs: every file together stays under 64 MB
+
+
+def dump_outputs(out_dir, pool, digest):
+    """--dump-outputs: the arrays a caller of the timed path (pool_scan) holds
+    after the last timed step -- page, metapage, 4 MiB slice and chunk-file
+    CRCs of this rank's pool and the per-copyset digests -- as <name>.npy.
+    CRCs are 32-bit values, so float64 (exact), not float32.  The small arrays
+    are written whole; when the page CRCs do not fit in what is left of the
+    64 MB, a fixed seeded sample of them is written, with its page indices in
+    page_crcs_index.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+
+    def host(t):
+        return t.cpu().numpy().view(np.uint32).astype(np.float64)
+
+    small = {"meta_crcs": host(pool.meta_crcs[: pool.n]), "slice_crcs": host(pool.slice_crcs),
+             "file_crcs": host(pool.file_crcs), "digest": host(digest)}
+    room = (DUMP_MAX_BYTES - sum(a.nbytes + 128 for a in small.values()) - 256) // 8
+    if room <= 0:
+        raise SystemExit("--dump-outputs: this pool's slice and file CRCs alone exceed 64 MB; use fewer --chunks")
+    pages = host(pool.page_crcs)
+    stale = os.path.join(out_dir, "page_crcs_index.npy")
+    if os.path.exists(stale):
+        os.remove(stale)  # an earlier, sampled dump into the same directory
+    if pages.size > room:
+        idx = np.sort(np.random.default_rng(0xD0).choice(pages.size, room // 2, replace=False))
+        small["page_crcs_index"] = idx.astype(np.float64)
+        pages = pages[idx]
+    small["page_crcs"] = pages
+    for name, a in small.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 TIMED = {}
 
 
@@ -1068,6 +1117,9 @@ def main():
     chunk, meta_sz = C.CHUNK_SIZE, C.META_PAGE_SIZE
     n = args.chunks
     log(rank, f"world={world} chunks/gpu={n} ({n * chunk / GiB:.1f} GiB data per GPU)")
+    # seeded (per rank): the same arguments give the same pool in every run, so
+    # the outputs of two builds (--dump-outputs) can be compared array for array
+    torch.manual_seed(0xC0FFEE + rank)
     data = torch.empty((n, chunk), dtype=torch.uint8, device=dev)
     data.random_(0, 256)
     meta = torch.zeros((n, meta_sz), dtype=torch.uint8, device=dev)
@@ -1172,14 +1224,17 @@ def main():
         t = torch.tensor([el], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
+    final_digest = full_digest[0] if (world > 1 and comm is None) else digest
+    if rank == 0 and args.dump_outputs:
+        # before anything below runs: the --full legs write into the pool
+        dump_outputs(args.dump_outputs, pool, final_digest)
     digest_check = None
-    if world > 1 and comm is not None:
+    if args.full and world > 1 and comm is not None:
         # untimed cross-check: the native RCCL digests == torch.distributed's
         native = digest.clone()
         local = torch.zeros_like(digest)
         pool_scan(pool, after_mult, group, local, comm=None, stream=stream)
         digest_check = bool(torch.equal(native, reduce_digests(local, dist)))
-    final_digest = full_digest[0] if (world > 1 and comm is None) else digest
     kern_each = [a.elapsed_time(b) for a, b in ev]
     kern_ms = float(np.mean(kern_each))
     # every rank's mean page-kernel time: the aggregate roofline is set by the slowest
@@ -1190,57 +1245,58 @@ def main():
         dist.all_gather_into_tensor(ga, kt)
         rank_kern = [float(x) for x in ga.cpu().tolist()]
 
-    # verify pass (after the timed region, before any host-side work that idles
-    # the GPU): every page must match.  The clock floor first (the gather above
-    # and the host sync leave the GPU idle; round 4 timed the verify pass right
-    # after a host CRC check and read the clock ramp: 5,104 vs ~6,400 GiB/s),
-    # then 5 calls back to back, each between its own event pair.
-    cnt = torch.tensor([0, -1], dtype=torch.int64, device=dev)
-    warm_clock(lambda: C.page_verify(pool.data, pool.page_crcs, pb, counters=cnt), min(args.clock_warm_ms, 500.0))
-    vev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(5)]
-    for ve0, ve1 in vev:
-        ve0.record(stream)
-        C.page_verify(pool.data, pool.page_crcs, pb, counters=cnt)
-        ve1.record(stream)
-    torch.cuda.synchronize()
-    verify_each = [a.elapsed_time(b) for a, b in vev]
-    verify_ms = float(np.mean(verify_each))
-    bad = int(cnt[0].item())
-
-    # measured read ceiling of THIS device: pure nt read of the same 16 GiB, same stream
-    sink = torch.empty(2 * 1024 * 16, dtype=torch.int32, device=dev)
-    probe_ms = []
-    for r in range(6):
-        pe0, pe1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        pe0.record(stream)
-        C.hbm_read_probe(pool.data, sink)
-        pe1.record(stream)
+    if args.full:
+        # verify pass (after the timed region, before any host-side work that idles
+        # the GPU): every page must match.  The clock floor first (the gather above
+        # and the host sync leave the GPU idle; round 4 timed the verify pass right
+        # after a host CRC check and read the clock ramp: 5,104 vs ~6,400 GiB/s),
+        # then 5 calls back to back, each between its own event pair.
+        cnt = torch.tensor([0, -1], dtype=torch.int64, device=dev)
+        warm_clock(lambda: C.page_verify(pool.data, pool.page_crcs, pb, counters=cnt), min(args.clock_warm_ms, 500.0))
+        vev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(5)]
+        for ve0, ve1 in vev:
+            ve0.record(stream)
+            C.page_verify(pool.data, pool.page_crcs, pb, counters=cnt)
+            ve1.record(stream)
         torch.cuda.synchronize()
-        if r:
-            probe_ms.append(pe0.elapsed_time(pe1))
-    probe_gbs = pool.data.numel() / (float(np.mean(probe_ms)) * 1e-3) / 1e9
-    # the page kernel itself with its CRC arithmetic removed (same tiles, prefetch
-    # ring, dynamic tail, loads and CRC-sized stores): the ceiling for THIS schedule
-    lo_out = torch.empty(pool.data.numel() // 4096, dtype=torch.int32, device=dev)
-    lo_ms = []
-    for r in range(6):
-        pe0, pe1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        pe0.record(stream)
-        C.page_load_probe(pool.data, lo_out, stream=stream)
-        pe1.record(stream)
-        torch.cuda.synchronize()
-        if r:
-            lo_ms.append(pe0.elapsed_time(pe1))
-    del lo_out
-    load_only_gbs = pool.data.numel() // 4096 * ALG_BYTES_PER_PAGE / (float(np.mean(lo_ms)) * 1e-3) / 1e9
+        verify_each = [a.elapsed_time(b) for a, b in vev]
+        verify_ms = float(np.mean(verify_each))
+        bad = int(cnt[0].item())
 
-    # untimed, every N, after the device timings above (it idles the GPU for tens
-    # of ms): the exchanged digests of two copysets == the sorted-name chain of
-    # those copysets' files over the WHOLE pool, from the bytes by libcurvecrc's
-    # CPU primitive (each rank hashes its own files on the host; partials
-    # XOR-reduced over torch.distributed): the exchange checked against an
-    # independent computation, not only against another transport
-    cpu_digest = cpu_digest_check(pool, lay, lo, n, final_digest, dist if world > 1 else None, dev)
+        # measured read ceiling of THIS device: pure nt read of the same 16 GiB, same stream
+        sink = torch.empty(2 * 1024 * 16, dtype=torch.int32, device=dev)
+        probe_ms = []
+        for r in range(6):
+            pe0, pe1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            pe0.record(stream)
+            C.hbm_read_probe(pool.data, sink)
+            pe1.record(stream)
+            torch.cuda.synchronize()
+            if r:
+                probe_ms.append(pe0.elapsed_time(pe1))
+        probe_gbs = pool.data.numel() / (float(np.mean(probe_ms)) * 1e-3) / 1e9
+        # the page kernel itself with its CRC arithmetic removed (same tiles, prefetch
+        # ring, dynamic tail, loads and CRC-sized stores): the ceiling for THIS schedule
+        lo_out = torch.empty(pool.data.numel() // 4096, dtype=torch.int32, device=dev)
+        lo_ms = []
+        for r in range(6):
+            pe0, pe1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            pe0.record(stream)
+            C.page_load_probe(pool.data, lo_out, stream=stream)
+            pe1.record(stream)
+            torch.cuda.synchronize()
+            if r:
+                lo_ms.append(pe0.elapsed_time(pe1))
+        del lo_out
+        load_only_gbs = pool.data.numel() // 4096 * ALG_BYTES_PER_PAGE / (float(np.mean(lo_ms)) * 1e-3) / 1e9
+
+        # untimed, every N, after the device timings above (it idles the GPU for tens
+        # of ms): the exchanged digests of two copysets == the sorted-name chain of
+        # those copysets' files over the WHOLE pool, from the bytes by libcurvecrc's
+        # CPU primitive (each rank hashes its own files on the host; partials
+        # XOR-reduced over torch.distributed): the exchange checked against an
+        # independent computation, not only against another transport
+        cpu_digest = cpu_digest_check(pool, lay, lo, n, final_digest, dist if world > 1 else None, dev)
     shard_ranges = [[lo, hi]]
     if world > 1:
         st = torch.tensor([lo, hi], dtype=torch.int64, device="cpu" if backend == "gloo" else dev)
@@ -1260,9 +1316,9 @@ def main():
     value = per_step_bytes * args.steps / GiB / el
     achieved = launch_pages * ALG_BYTES_PER_PAGE / (kern_ms * 1e-3) / 1e9
     traffic, traffic_src = None, None
-    if rank == 0 and world == 1 and not args.no_pmc and pb == 4096:
+    if args.full and rank == 0 and world == 1 and not args.no_pmc and pb == 4096:
         traffic, traffic_src = live_traffic(n * chunk / GiB)
-    if traffic is None:  # the committed PMC summary of the same geometry
+    if args.full and traffic is None:  # the committed PMC summary of the same geometry
         why = traffic_src
         traffic, traffic_src = load_traffic(args)
         if traffic and abs(traffic / (launch_pages * ALG_BYTES_PER_PAGE) - 1.0) > 0.05:
@@ -1292,29 +1348,30 @@ def main():
                    "chunks_per_gpu": n, "page_bytes": pb, "copysets": N_COPYSETS,
                    "parallelism": f"chunk-range shard x{world}"},
         "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
+                     "frac": round(achieved / HBM_PEAK_GBS, 4),
                      "kernel": "page_crc_kernel<16,0>", "kernel_ms_avg": round(kern_ms, 4),
                      "kernel_ms_each": [round(x, 4) for x in kern_each],
                      "kernel_ms_median": round(float(np.median(kern_each)), 4),
                      "kernel_spread_pct": round((max(kern_each) - min(kern_each)) / min(kern_each) * 100, 2),
                      "alg_bytes_per_launch": launch_pages * ALG_BYTES_PER_PAGE,
                      "pages_per_launch": launch_pages,
-                     "metapages_in_launch": n if fused_meta else 0,
-                     "traffic_source": traffic_src,
-                     "read_probe_GBps": round(probe_gbs, 1),
-                     "frac_of_read_probe": round(achieved / probe_gbs, 4),
-                     "load_only_probe_GBps": round(load_only_gbs, 1),
-                     "frac_of_load_only_probe": round(achieved / load_only_gbs, 4)},
-        "verify": {"GiBps": round(n * chunk / GiB / (verify_ms * 1e-3), 2), "bad_pages": bad,
-                   "ms_avg": round(verify_ms, 4), "ms_each": [round(x, 4) for x in verify_each],
-                   "spread_pct": round((max(verify_each) - min(verify_each)) / min(verify_each) * 100, 2),
-                   "alg_frac_of_hbm_peak": round(n_pages * (pb + 4) / (verify_ms * 1e-3) / 1e9
-                                                 / HBM_PEAK_GBS, 4),
-                   "note": "cc_page_verify_dev over the pool after a clock floor; alg bytes = 4096 read + "
-                           "4 expected CRC read per page"},
+                     "metapages_in_launch": n if fused_meta else 0},
         "shard_ranges": shard_ranges,
     }
-    out["digest_check_cpu"] = cpu_digest
+    if args.full:
+        out["roofline"].update({"traffic": traffic, "traffic_source": traffic_src,
+                                "read_probe_GBps": round(probe_gbs, 1),
+                                "frac_of_read_probe": round(achieved / probe_gbs, 4),
+                                "load_only_probe_GBps": round(load_only_gbs, 1),
+                                "frac_of_load_only_probe": round(achieved / load_only_gbs, 4)})
+        out["verify"] = {"GiBps": round(n * chunk / GiB / (verify_ms * 1e-3), 2), "bad_pages": bad,
+                         "ms_avg": round(verify_ms, 4), "ms_each": [round(x, 4) for x in verify_each],
+                         "spread_pct": round((max(verify_each) - min(verify_each)) / min(verify_each) * 100, 2),
+                         "alg_frac_of_hbm_peak": round(n_pages * (pb + 4) / (verify_ms * 1e-3) / 1e9
+                                                       / HBM_PEAK_GBS, 4),
+                         "note": "cc_page_verify_dev over the pool after a clock floor; alg bytes = 4096 read + "
+                                 "4 expected CRC read per page"}
+        out["digest_check_cpu"] = cpu_digest
     out["numa_binding_rank0"] = numa
     if world > 1:
         if comm is not None:
@@ -1331,13 +1388,15 @@ def main():
         dist.all_gather_into_tensor(xg, xt)
         rank_x = [float(v) for v in xg.cpu().tolist()]
         step_ms = el / args.steps * 1e3
-        out["digest_exchange"] = {"path": comm_note, "matches_torch_distributed": digest_check,
-                                  "matches_cpu_chain": cpu_digest["ok"],
+        out["digest_exchange"] = {"path": comm_note,
                                   "ms_each": [round(x, 4) for x in x_each], "ms_avg": round(x_ms, 4),
                                   "share_of_step": round(x_ms / step_ms, 4),
                                   "rank_ms_avg": [round(x, 4) for x in rank_x],
                                   "share_of_step_max_rank": round(max(rank_x) / step_ms, 4),
                                   "timing": x_how}
+        if args.full:
+            out["digest_exchange"].update({"matches_torch_distributed": digest_check,
+                                           "matches_cpu_chain": cpu_digest["ok"]})
         # aggregate roofline over the node: every rank's algorithmic bytes over the
         # slowest rank's page-kernel time, against N x the per-GPU peak
         agg = world * launch_pages * ALG_BYTES_PER_PAGE / (max(rank_kern) * 1e-3) / 1e9
@@ -1347,22 +1406,23 @@ def main():
                                 "rank_kernel_ms_min": round(min(rank_kern), 4),
                                 "rank_kernel_ms_max": round(max(rank_kern), 4),
                                 "note": "frac/achieved/kernel_ms_* are rank 0's; aggregate_* use every rank"})
-    if rank == 0 and world == 1 and args.updates:
+    solo = args.full and rank == 0 and world == 1  # the legs below: --full, one GPU
+    if solo and args.updates:
         out["partial_write"] = partial_write_leg(pool, args)
-    if rank == 0 and world == 1 and args.reads:
+    if solo and args.reads:
         out["read_verify"] = read_verify_leg(pool, args)
-    if rank == 0 and world == 1 and args.wal_entries:
+    if solo and args.wal_entries:
         out["wal_replay"] = wal_replay_leg(pool, args)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if solo and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(pool, args, rank)
-    if world > 1 and not args.no_e2e and args.stream_chunks:
+    if args.full and world > 1 and not args.no_e2e and args.stream_chunks:
         # BASELINE config 5 streamed end to end: every rank scans its own chunk
         # files from pinned host memory through its own PCIe link
         try:
             out["stream_all_ranks"] = stream_all_ranks_leg(args, rank, world, dev)
         except Exception as e:  # report, never lose the main line
             out["stream_all_ranks"] = {"error": repr(e)}
-    if rank == 0 and world == 1 and not args.no_e2e:
+    if solo and not args.no_e2e:
         out["e2e_pinned_GiBps"] = e2e_leg(args, dev)
         if args.stream_chunks:
             try:

@@ -4,7 +4,7 @@
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-/root/repo}" || exit 1
 mkdir -p gpurun_out
-COMMON="--steps 2 --warmup 1 --chunks 64 --updates 0 --reads 0 --wal-entries 0 --file-chunks 0 --no-cpu-baseline --no-pmc"
+COMMON="--steps 2 --warmup 1 --chunks 64 --full --updates 0 --reads 0 --wal-entries 0 --file-chunks 0 --no-cpu-baseline --no-pmc"
 for D in 1024 10000; do
   T0=$(date +%s)
   timeout -k 10 400 python -u bench.py $COMMON --stream-distinct $D > gpurun_out/stream_d$D.json 2> gpurun_out/stream_d$D.err || { tail -30 gpurun_out/stream_d$D.err; exit 1; }

@@ -17,7 +17,7 @@ fi
 OUT=$R/gpurun_out/prof_$TAG
 rm -rf $OUT && mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 500 rocprofv3 --kernel-trace --stats -d $OUT/trace -o run --output-format csv -- python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --no-pmc --no-e2e --no-cpu-baseline > $OUT/trace_bench.log 2>&1 || { echo PROFFAIL; tail -20 $OUT/trace_bench.log; exit 1; }
+timeout -k 10 500 rocprofv3 --kernel-trace --stats -d $OUT/trace -o run --output-format csv -- python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --full --no-pmc --no-e2e --no-cpu-baseline > $OUT/trace_bench.log 2>&1 || { echo PROFFAIL; tail -20 $OUT/trace_bench.log; exit 1; }
 S=$(find $OUT/trace -name "*kernel_stats.csv" | head -1)
 T=$(find $OUT/trace -name "*kernel_trace.csv" | head -1)
 cp "$S" $R/gpurun_out/rocprof_kernel_stats_$TAG.csv

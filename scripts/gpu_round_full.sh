@@ -7,8 +7,10 @@ TAG=${1:-r01}
 mkdir -p $R/gpurun_out
 timeout -k 10 400 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread > $R/gpurun_out/gpu_tests_$TAG.log 2>&1 || { echo TESTFAIL; tail -30 $R/gpurun_out/gpu_tests_$TAG.log; exit 1; }
 tail -1 $R/gpurun_out/gpu_tests_$TAG.log
-timeout -k 10 400 python -u bench.py > $R/gpurun_out/bench_$TAG.log 2>&1 || { echo BENCHFAIL; tail -30 $R/gpurun_out/bench_$TAG.log; exit 1; }
-tail -1 $R/gpurun_out/bench_$TAG.log > $R/gpurun_out/bench_$TAG.json
+O=${ROUND_OUT:-$R/build/round_$TAG}  # the bench line with every leg (--full) and its log
+mkdir -p $O
+timeout -k 10 400 python -u bench.py --full > $O/bench_$TAG.log 2>&1 || { echo BENCHFAIL; tail -30 $O/bench_$TAG.log; exit 1; }
+tail -1 $O/bench_$TAG.log > $O/bench_$TAG.json
 bash $R/scripts/gpu_profile.sh $TAG 20 || { echo PROFFAIL; exit 1; }
 cd /tmp && export TMPDIR=/tmp
 rm -rf $R/gpurun_out/prof_log_$TAG

@@ -15,7 +15,7 @@ TAG=world8_full
 if [ "${1:-}" = stub ]; then EXTRA="CURVE_AMD_LIB=$R/build/stub/libcurvecrc_stubrccl.so"; TAG=world8_full_stub; fi
 P=$(python3 -c "import socket; s=socket.socket(); s.bind(('127.0.0.1',0)); print(s.getsockname()[1])")
 env BENCH_DIST_BACKEND=gloo $EXTRA timeout -k 10 900 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 8 \
-    --master-addr 127.0.0.1 --master-port $P bench.py --gpus 8 --steps 20 --warmup 5 \
+    --master-addr 127.0.0.1 --master-port $P bench.py --gpus 8 --steps 20 --warmup 5 --full \
     > $R/gpurun_out/$TAG.log 2>&1
 rc=$?
 kill $TICK

@@ -6,6 +6,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 from conftest import ROOT
 
 
@@ -16,6 +18,46 @@ def test_world_size_mismatch_refused():
     assert p.returncode == 2, p.stderr[-2000:]
     line = json.loads(p.stdout.strip().splitlines()[-1])
     assert "WORLD_SIZE=2" in line["error"]
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_the_same_outputs_twice(tmp_path):
+    """A plain run (no --full) times exactly --steps steps and prints the headline
+    line without the --full legs; --dump-outputs writes the last step's CRCs and
+    digests as float64 .npy (32-bit values, exact), and a second run with the
+    same arguments writes the same arrays: the pool is seeded."""
+    import numpy as np
+    torch = pytest.importorskip("torch")
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    chunks, steps = 16, 2
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"dump{k}"
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--chunks", str(chunks),
+                            "--steps", str(steps), "--warmup", "1", "--clock-warm-ms", "0", "--dump-outputs", str(d)],
+                           cwd=str(tmp_path), capture_output=True, text=True, timeout=300)
+        assert p.returncode == 0, p.stderr[-2000:]
+        line = json.loads(p.stdout.strip().splitlines()[-1])
+        assert line["steps"] == steps and len(line["roofline"]["kernel_ms_each"]) == steps
+        assert line["ms_per_step"] > 0 and line["value"] > 0 and line["unit"] == "GiB/s"
+        assert abs(line["value"] - chunks * (16 << 20) / (1 << 30) / (line["ms_per_step"] * 1e-3)) <= 0.01 * line["value"]
+        for leg in ("verify", "cpu_baseline", "partial_write", "read_verify", "wal_replay", "stream", "files",
+                    "scan_op", "digest_check_cpu"):
+            assert leg not in line, leg
+        arrays = {f: np.load(str(d / f)) for f in sorted(os.listdir(d))}
+        assert {f: a.shape for f, a in arrays.items()} == {
+            "digest.npy": (min(64, chunks),), "file_crcs.npy": (chunks,), "meta_crcs.npy": (chunks,),
+            "page_crcs.npy": (chunks * 4096,), "slice_crcs.npy": (chunks * 4,)}
+        assert all(a.dtype == np.float64 for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64_000_000
+        dumps.append(arrays)
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f
+    # not all zero, and every value a 32-bit integer
+    pages = dumps[0]["page_crcs.npy"]
+    assert len(np.unique(pages)) > pages.size // 2
+    assert (pages == np.floor(pages)).all() and pages.min() >= 0 and pages.max() < 2**32
 
 
 def test_numa_binding_helpers_never_fail():

@@ -204,7 +204,7 @@ def _bench_world8(tmp_path, log_name, extra_env=None):
     world, chunks = 8, 16
     env = dict(os.environ, BENCH_DIST_BACKEND="gloo", BENCH_DIST_TIMEOUT_S="240", **(extra_env or {}))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", str(world), "--chunks", str(chunks),
-           "--steps", "3", "--warmup", "1", "--clock-warm-ms", "0", "--comm-timeout-ms", "5000", "--no-pmc",
+           "--steps", "3", "--warmup", "1", "--clock-warm-ms", "0", "--comm-timeout-ms", "5000", "--full", "--no-pmc",
            "--stream-chunks-per-rank", "4", "--file-chunks", "0"]
     # the ranks' output goes to a file that grows while they run (a GPU box's
     # runner takes a call that prints nothing for minutes to be hung)
