@@ -86,6 +86,15 @@ class CcPoolShard(ctypes.Structure):  # include/curve_crc.h cc_pool_shard
                 ("ev_pages_end", _vp), ("ev_exchange_begin", _vp), ("ev_exchange_end", _vp)]
 
 
+class CcCow(ctypes.Structure):
+    """cc_cow (include/curve_crc.h): the snapshot slots of a cc_apply_log_cow_dev call
+    (a host struct of device pointers)."""
+    _fields_ = [("chunk_bytes", _u32), ("n_slots", _u32), ("d_snap_slot", _vp), ("d_snap", _vp),
+                ("d_snap_crcs", _vp), ("d_snap_bitmap", _vp), ("d_copied", _vp), ("d_stale", _vp)]
+
+
+CC_NO_SNAPSHOT = 0xFFFFFFFF
+
 SIGNATURES = {
     "crc32c_value": (_u32, [_vp, _sz]),
     "crc32c_extend": (_u32, [_u32, _vp, _sz]),
@@ -126,6 +135,11 @@ SIGNATURES = {
     "cc_apply_log_work_bytes": (_u64, [_u64, _u32, _u32]),
     "cc_apply_log_dev": (_int, [_vp, _u64, _u32, _vp, _vp, _u64, _u32, _vp, _vp, _u64, _vp]),
     "cc_apply_log_delta_dev": (_int, [_vp, _u64, _u32, _vp, _vp, _u64, _u32, _vp, _vp, _u64, _vp]),
+    "cc_apply_log_cow_dev": (_int, [_vp, _u64, _u32, _vp, _vp, _u64, _u32, _vp, _vp, _u64, _vp, _int,
+                                    ctypes.POINTER(CcCow)]),
+    "cc_snap_meta_encode": (_int, [_u64, _int, _u32, _vp, _vp, _u32]),
+    "cc_snap_meta_decode": (_int, [_vp, _u32, ctypes.POINTER(_u64), ctypes.POINTER(_int), ctypes.POINTER(_u32), _vp,
+                                   _u32]),
     "cc_engine_stream_entries": (_u64, []),
     "cc_apply_log_probe_dev": (_int, [_vp, _u64, _vp, _vp, _u64, _vp, _vp]),
     "cc_apply_logs_work_bytes": (_u64, [_u64, _u32, _u32]),

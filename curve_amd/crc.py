@@ -486,6 +486,105 @@ def apply_log(pool, page_crcs, src, d_log, n_updates: int, max_len: int, page_by
     return 1
 
 
+class Cow:
+    """The snapshot slots of apply_log_cow (cc_cow, include/curve_crc.h), as
+    device tensors for a pool of `n_chunks` chunks of `chunk_bytes`:
+      snap_slot int32 [n_chunks]   chunk c's slot, or -1 (CC_NO_SNAPSHOT; the default)
+      snap      uint8 [n_slots, chunk_bytes]
+      snap_crcs int32 [n_slots, pages_per_chunk]
+      bitmap    int32 [n_slots, ceil(pages_per_chunk / 32)]  (a row's bytes are SnapshotMetaPage's bitmap)
+      copied, stale int64 [1]      running counts (stale only with verify=True:
+                                   the pass then rehashes what it copies)
+    `fill` / `crc_fill` initialise snap and snap_crcs (tests use sentinels)."""
+
+    def __init__(self, n_chunks: int, chunk_bytes: int, page_bytes: int = PAGE_SIZE, n_slots: int = 1, device=None,
+                 verify: bool = False, fill: int = 0, crc_fill: int = 0):
+        torch = _torch()
+        if chunk_bytes <= 0 or chunk_bytes % page_bytes:
+            raise CurveCrcError(_lib.CC_EINVAL, "chunk_bytes must be a multiple of page_bytes")
+        dev = device if device is not None else torch.device("cuda", torch.cuda.current_device())
+        self.n_chunks, self.chunk_bytes, self.page_bytes, self.n_slots = n_chunks, chunk_bytes, page_bytes, n_slots
+        self.pages_per_chunk = chunk_bytes // page_bytes
+        self.words_per_slot = (self.pages_per_chunk + 31) // 32
+        self.snap_slot = torch.full((n_chunks,), -1, dtype=torch.int32, device=dev)
+        self.snap = torch.full((n_slots, chunk_bytes), fill, dtype=torch.uint8, device=dev)
+        self.snap_crcs = torch.full((n_slots, self.pages_per_chunk), crc_fill, dtype=torch.int32, device=dev)
+        self.bitmap = torch.zeros((n_slots, self.words_per_slot), dtype=torch.int32, device=dev)
+        self.copied = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.stale = torch.zeros(1, dtype=torch.int64, device=dev) if verify else None
+
+    def struct(self) -> "_lib.CcCow":
+        c = _lib.CcCow()
+        c.chunk_bytes, c.n_slots = self.chunk_bytes, self.n_slots
+        c.d_snap_slot = _dev_ptr(self.snap_slot, "snap_slot")
+        c.d_snap = _dev_ptr(self.snap, "snap")
+        c.d_snap_crcs = _dev_ptr(self.snap_crcs, "snap_crcs")
+        c.d_snap_bitmap = _dev_ptr(self.bitmap, "bitmap")
+        c.d_copied = _dev_ptr(self.copied, "copied")
+        c.d_stale = _dev_ptr(self.stale, "stale") if self.stale is not None else None
+        return c
+
+    def slot_bitmap_bytes(self, slot: int) -> bytes:
+        """Slot `slot`'s bitmap as SnapshotMetaPage holds it (snap_meta_encode's `bitmap`)."""
+        return self.bitmap[slot].cpu().numpy().tobytes()[:(self.pages_per_chunk + 7) // 8]
+
+
+def apply_log_cow(pool, page_crcs, src, d_log, n_updates: int, max_len: int, cow: Optional[Cow],
+                  page_bytes: int = PAGE_SIZE, stream=None, delta: bool = False):
+    """cc_apply_log_cow_dev: apply_log (delta or not) for chunks with an open
+    snapshot -- before the writes land, every touched page whose chunk has a
+    slot in `cow` and whose bit in the slot's bitmap is clear is copied into the
+    slot with its stored CRC (page_crcs must hold the CRCs before the batch) and
+    its bit set.  cow=None is apply_log."""
+    torch = _torch()
+    need = int(lib().cc_apply_log_work_bytes(n_updates, max_len, page_bytes))
+    if need == 0:
+        raise CurveCrcError(_lib.CC_EINVAL, "unsupported log geometry")
+    key = _stream_key(pool.device, stream)
+    work = _log_work.get(key)
+    if work is None or work.numel() < need:
+        with _on_stream(stream):
+            work = torch.empty(need, dtype=torch.uint8, device=pool.device)
+        _log_work[key] = work
+    cs = cow.struct() if cow is not None else None
+    with torch.cuda.device(pool.device):
+        check(lib().cc_apply_log_cow_dev(_dev_ptr(pool, "pool"), _nbytes(pool), page_bytes, _dev_ptr(src, "src"),
+                                         _dev_ptr(d_log, "log"), n_updates, max_len,
+                                         _dev_ptr(page_crcs, "page_crcs"), _dev_ptr(work, "work"), work.numel(),
+                                         _stream_handle(stream), 1 if delta else 0,
+                                         ctypes.byref(cs) if cs is not None else None), "cc_apply_log_cow_dev")
+    if stream is not None:
+        work.record_stream(stream)
+        if cow is not None:
+            for t in (cow.snap_slot, cow.snap, cow.snap_crcs, cow.bitmap, cow.copied, cow.stale):
+                if t is not None:
+                    t.record_stream(stream)
+    return 1
+
+
+def snap_meta_encode(sn: int, bitmap: bytes, bits: int, page_bytes: int = META_PAGE_SIZE,
+                     damaged: bool = False) -> bytes:
+    """cc_snap_meta_encode: the snapshot file's metapage (SnapshotMetaPage::encode)
+    for `bits` blocks whose bitmap bytes are `bitmap` (Cow.slot_bitmap_bytes)."""
+    bitmap = bytes(bitmap)
+    if len(bitmap) < (bits + 7) // 8:
+        raise CurveCrcError(_lib.CC_EINVAL, "bitmap shorter than bits")
+    out = ctypes.create_string_buffer(page_bytes)
+    check(lib().cc_snap_meta_encode(sn, 1 if damaged else 0, bits, bitmap, out, page_bytes), "cc_snap_meta_encode")
+    return out.raw
+
+
+def snap_meta_decode(buf: bytes):
+    """cc_snap_meta_decode -> (sn, damaged, bits, bitmap bytes); CurveCrcError
+    (CC_ECORRUPT) for a bad CRC, version or length."""
+    buf = bytes(buf)
+    sn, damaged, bits = ctypes.c_uint64(), ctypes.c_int(), ctypes.c_uint32()
+    bm = ctypes.create_string_buffer(max(len(buf), 1))
+    check(lib().cc_snap_meta_decode(buf, len(buf), ctypes.byref(sn), ctypes.byref(damaged), ctypes.byref(bits), bm,
+                                    len(buf)), "cc_snap_meta_decode")
+    return int(sn.value), bool(damaged.value), int(bits.value), bm.raw[:(bits.value + 7) // 8]
+
+
 def read_pages_list(offs, lens, page_bytes: int = PAGE_SIZE):
     """Diagnostic helper (host): the pages a batch of reads touches, read after
     read -- the list cc_page_list_probe_dev walks (int64 page indices; an empty

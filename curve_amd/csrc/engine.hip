@@ -1495,8 +1495,13 @@ uint64_t cc_apply_log_work_bytes(uint64_t n_updates, uint32_t max_len, uint32_t 
 namespace {
 int apply_log(void* d_pool, uint64_t pool_bytes, uint32_t page_bytes, const void* d_src, const cc_update* d_log,
               uint64_t n_updates, uint32_t max_len, uint32_t* d_page_crcs, void* d_work, uint64_t work_bytes,
-              void* stream, int delta) {
+              void* stream, int delta, const cc_cow* cow = nullptr) {
     if (!log_page_ok(page_bytes)) return CC_EINVAL;
+    if (cow) {
+        if (cow->chunk_bytes == 0 || cow->chunk_bytes % page_bytes || pool_bytes % cow->chunk_bytes) return CC_EINVAL;
+        if (!cow->d_snap_slot || !cow->d_snap || !cow->d_snap_crcs || !cow->d_snap_bitmap) return CC_EINVAL;
+        if ((uintptr_t)cow->d_snap & 3u) return CC_EINVAL;
+    }
     if (n_updates == 0) return CC_OK;
     if (!d_pool || !d_src || !d_log || !d_page_crcs || !d_work || max_len == 0) return CC_EINVAL;
     if (pool_bytes % page_bytes || ((uintptr_t)d_pool & 3u) || ((uintptr_t)d_src & 3u)) return CC_EINVAL;
@@ -1533,7 +1538,8 @@ int apply_log(void* d_pool, uint64_t pool_bytes, uint32_t page_bytes, const void
     a.blocks = (int)(blocks < (uint64_t)c->cus ? (blocks ? blocks : 1) : (uint64_t)c->cus);
     hipError_t e;
     // logs of up to 64 writes (each within one page's length) take the one-launch path
-    if (n_updates <= 64 && a.slots <= 2) return map_err(launch_log_small(a, s));
+    // (copy on write needs the head records: always insert -> cow -> pages)
+    if (!cow && n_updates <= 64 && a.slots <= 2) return map_err(launch_log_small(a, s));
     // (memset + insert + pages as ONE cooperative launch with two grid barriers
     // measured 0.221 vs 0.162 ms a batch: not kept)
     std::lock_guard<std::mutex> lk(c->log_mu);
@@ -1555,6 +1561,35 @@ int apply_log(void* d_pool, uint64_t pool_bytes, uint32_t page_bytes, const void
         a.table_mask = (uint32_t)(lw.table_entries - 1);
     }
     e = launch_log_insert(a, s);
+    if (cow && e == hipSuccess) {
+        // the pages' old bytes and CRCs into their snapshots before the page kernel overwrites them
+        LogCowLaunch w = {};
+        w.pool = a.pool;
+        w.table = a.table;
+        w.heads = a.heads;
+        w.seg_count = a.seg_count;
+        w.seg_cap = a.seg_cap;
+        w.n_segs = a.n_segs;
+        w.n_pages = (uint32_t)n_pages;
+        w.page_bytes = page_bytes;
+        w.pages_per_chunk = cow->chunk_bytes / page_bytes;
+        w.words_per_slot = (w.pages_per_chunk + 31u) / 32u;
+        w.n_slots = cow->n_slots;
+        w.snap_slot = cow->d_snap_slot;
+        w.snap = static_cast<unsigned char*>(cow->d_snap);
+        w.snap_crcs = cow->d_snap_crcs;
+        w.snap_bitmap = cow->d_snap_bitmap;
+        w.page_crcs = d_page_crcs;
+        w.copied = reinterpret_cast<unsigned long long*>(cow->d_copied);
+        w.stale = reinterpret_cast<unsigned long long*>(cow->d_stale);
+        w.image = c->image;
+        w.kconst = a.kconst;
+        // a wave per touched page up to one workgroup per CU (the rehash fills the CU's LDS), two without it
+        const uint64_t wb = (lw.n_pieces + kCowWaves - 1) / kCowWaves;
+        const uint64_t cap = (uint64_t)c->cus * (cow->d_stale ? 1u : 2u);
+        w.blocks = (int)(wb < cap ? (wb ? wb : 1) : cap);
+        e = launch_log_cow(w, s);
+    }
     if (e == hipSuccess) e = launch_log_pages(a, s);
     if (t && e != hipSuccess) t->dirty = true;  // the insert may have run: clear before the next use
     if (tmp) {
@@ -1577,6 +1612,13 @@ int cc_apply_log_delta_dev(void* d_pool, uint64_t pool_bytes, uint32_t page_byte
                            void* d_work, uint64_t work_bytes, void* stream) {
     return apply_log(d_pool, pool_bytes, page_bytes, d_src, d_log, n_updates, max_len, d_page_crcs, d_work,
                      work_bytes, stream, 1);
+}
+
+int cc_apply_log_cow_dev(void* d_pool, uint64_t pool_bytes, uint32_t page_bytes, const void* d_src,
+                         const cc_update* d_log, uint64_t n_updates, uint32_t max_len, uint32_t* d_page_crcs,
+                         void* d_work, uint64_t work_bytes, void* stream, int delta, const cc_cow* cow) {
+    return apply_log(d_pool, pool_bytes, page_bytes, d_src, d_log, n_updates, max_len, d_page_crcs, d_work,
+                     work_bytes, stream, delta ? 1 : 0, cow);
 }
 
 // ---- a queue of write logs, pipelined (cc_apply_logs_dev) ----

@@ -226,6 +226,41 @@ int cc_chunk_meta_sn(const void* metapage, uint32_t bytes, uint64_t* sn) {
     return CC_OK;
 }
 
+// SnapshotMetaPage::encode/decode (datastore/chunkserver_snapshot.cpp:30-82):
+// version u8 | damaged u8 | sn u64 | bits u32 | bitmap | CRC32 of the above
+int cc_snap_meta_encode(uint64_t sn, int damaged, uint32_t bits, const void* bitmap, void* out, uint32_t out_bytes) {
+    if (!bitmap || !out) return CC_EINVAL;
+    const uint64_t nb = ((uint64_t)bits + 7) >> 3;
+    if (14 + nb + 4 > out_bytes) return CC_EINVAL;
+    unsigned char* p = static_cast<unsigned char*>(out);
+    p[0] = 1;  // FORMAT_VERSION (datastore/define.h:39)
+    p[1] = damaged ? 1 : 0;
+    put64(p + 2, sn);
+    put32(p + 10, bits);
+    memcpy(p + 14, bitmap, nb);
+    put32(p + 14 + nb, crc32c_value(p, 14 + nb));
+    memset(p + 14 + nb + 4, 0, out_bytes - (14 + nb + 4));
+    return CC_OK;
+}
+
+int cc_snap_meta_decode(const void* buf, uint32_t bytes, uint64_t* sn, int* damaged, uint32_t* bits, void* bitmap,
+                        uint32_t bitmap_cap_bytes) {
+    if (!buf) return CC_EINVAL;
+    const unsigned char* p = static_cast<const unsigned char*>(buf);
+    if (bytes < 18) return CC_ECORRUPT;
+    const uint32_t nbits = get32(p + 10);
+    const uint64_t nb = ((uint64_t)nbits + 7) >> 3;
+    if (14 + nb + 4 > bytes) return CC_ECORRUPT;  // a bitmap that cannot fit the page
+    if (crc32c_value(p, 14 + nb) != get32(p + 14 + nb)) return CC_ECORRUPT;
+    if (p[0] != 1) return CC_ECORRUPT;
+    if (bitmap && nb > bitmap_cap_bytes) return CC_EINVAL;
+    if (sn) *sn = get64(p + 2);
+    if (damaged) *damaged = p[1] ? 1 : 0;
+    if (bits) *bits = nbits;
+    if (bitmap) memcpy(bitmap, p + 14, nb);
+    return CC_OK;
+}
+
 int cc_pcrc_is_racy(const cc_pcrc_header* h) {
     if (!h) return CC_EINVAL;
     // closed boundary (git's >=): the coarse clock may lag a write by a full tick

@@ -179,6 +179,35 @@ hipError_t launch_log_insert(const LogLaunch& a, hipStream_t s);
 hipError_t launch_log_pages(const LogLaunch& a, hipStream_t s);
 // <= 64 writes of <= 2 pieces each in one launch (no table, no insert)
 hipError_t launch_log_small(const LogLaunch& a, hipStream_t s);
+// Copy on write (cc_apply_log_cow_dev): between launch_log_insert and
+// launch_log_pages, one wave per head record copies the page's old bytes and
+// its stored CRC into its chunk's snapshot slot unless the slot's bitmap
+// already holds the page.  Reads the table and the head records only.
+constexpr int kCowWaves = 16;  // waves per workgroup of log_cow_kernel<M, Verify>
+struct LogCowLaunch {
+    const unsigned char* pool;
+    const uint64_t* table;      // LogLaunch::table after the insert: page = entry >> 32, minus 1
+    const uint32_t* heads;      // LogLaunch::heads / seg_count / seg_cap / n_segs
+    const uint32_t* seg_count;
+    uint32_t seg_cap;
+    uint32_t n_segs;
+    uint32_t n_pages;           // pool pages
+    uint32_t page_bytes;
+    uint32_t pages_per_chunk;
+    uint32_t words_per_slot;    // bitmap words a slot: ceil(pages_per_chunk / 32)
+    uint32_t n_slots;
+    const uint32_t* snap_slot;  // [chunks] slot of the chunk's open snapshot (>= n_slots: none)
+    unsigned char* snap;        // n_slots x chunk
+    uint32_t* snap_crcs;        // n_slots x pages_per_chunk
+    uint32_t* snap_bitmap;      // n_slots x words_per_slot
+    const uint32_t* page_crcs;  // the pool's CRC table before the batch
+    unsigned long long* copied; // += pages copied, or null
+    unsigned long long* stale;  // += copied pages whose bytes mismatch page_crcs (null: no rehash, no LDS image)
+    const void* image;
+    uint32_t kconst;
+    int blocks;
+};
+hipError_t launch_log_cow(const LogCowLaunch& a, hipStream_t s);
 // diagnostic: the write log's page traffic alone (4 KiB pages; kernels.hip log_probe_kernel)
 struct LogProbeDesc {
     uint64_t page;      // touched page

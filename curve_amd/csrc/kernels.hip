@@ -1736,6 +1736,144 @@ __global__ __launch_bounds__(64 * log_waves(M, Delta)) void log_pages_kernel(Log
     log_pages_body<M, Delta>(a, tab);
 }
 
+// Copy on write (cc_apply_log_cow_dev), between the insert and the page kernel:
+// CSChunkFile::Write's copy2Snapshot for a whole batch.  The heads are cut into
+// equal shares per workgroup and per wave, as in log_pages_body; lane k of a
+// wave step takes head base + k: its page (table[slot] >> 32), the page's chunk,
+// the chunk's snapshot slot and its bit in the slot's bitmap.  A page with a
+// slot below n_slots and a clear bit is copied: the lane sets the bit (one
+// atomicOr: 32 pages share a word and sit in other lanes and waves) and moves
+// the page's stored CRC; the wave then copies the marked pages two at a time,
+// lane l holding dwords l + 64 j of each (whole 256-byte rows, load_page's
+// layout).  Verify also rehashes every copied page and counts those whose
+// bytes do not match the stored CRC (still copied with it); without it the
+// kernel takes no LDS and does no CRC arithmetic.  No spin waits, nothing
+// shared between workgroups but the bitmap words and the two counters (one
+// atomicAdd a wave each).
+template <int M, bool Verify>
+__global__ __launch_bounds__(64 * kCowWaves) void log_cow_kernel(LogCowLaunch a) {
+    __shared__ uint32_t tab[Verify ? kLdsBytes / 4 : 1];
+    constexpr int kSpl = kInsertBlocks / 64;
+    constexpr uint32_t pb = 256u * M;  // = a.page_bytes (launch_log_cow picks M)
+    const uint32_t lane = threadIdx.x & 63u;
+    // the insert blocks' segment counts, as in log_pages_body: lane l holds
+    // segments kSpl * l .. kSpl * l + kSpl - 1, scum = inclusive prefix of the lanes' sums
+    uint32_t sc[kSpl];
+    uint32_t ssum = 0;
+#pragma unroll
+    for (int j = 0; j < kSpl; j++) {
+        const uint32_t sg = kSpl * lane + j;
+        sc[j] = sg < a.n_segs ? a.seg_count[sg] : 0u;
+        ssum += sc[j];
+    }
+    uint32_t scum = ssum;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t o = __shfl_up(scum, d, 64);
+        if (lane >= (uint32_t)d) scum += o;
+    }
+    const uint32_t sexcl = scum - ssum;
+    const uint32_t Hall = __builtin_amdgcn_readlane(scum, 63);
+    const uint32_t hb0 = (uint32_t)((uint64_t)Hall * blockIdx.x / gridDim.x);
+    const uint32_t hb1 = (uint32_t)((uint64_t)Hall * (blockIdx.x + 1) / gridDim.x);
+    if (hb0 >= hb1) return;  // (uniform over the workgroup)
+    if constexpr (Verify) fill_lds<64 * kCowWaves>(tab, static_cast<const uint4*>(a.image));
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t c0 = lane << 2 & 0x7Cu;
+    const uint32_t c1 = c0 | 0x10000u;
+    const uint32_t cf = kFinBase + (lane << 2);
+    const uint32_t Hb = hb1 - hb0;
+    const uint32_t first = hb0 + (uint32_t)((uint64_t)Hb * wave / kCowWaves);
+    const uint32_t H = hb0 + (uint32_t)((uint64_t)Hb * (wave + 1) / kCowWaves);  // this wave: [first, H)
+    uint32_t ncopied = 0, nstale = 0;
+    for (uint32_t base = first; base < H; base += 64u) {
+        const uint64_t ih = (uint64_t)base + lane;
+        const bool hv = ih < H;
+        const uint32_t hi = hv ? (uint32_t)ih : base;  // (clamped: the loads below need no branch)
+        // the lane's head in its segment: the first lane tl with scum > hi holds
+        // the segment (a binary search over the lanes), then its kSpl counts
+        uint32_t lo = 0, up = 63;
+#pragma unroll
+        for (int st = 0; st < 6; st++) {
+            const uint32_t mid = (lo + up) >> 1;
+            const bool le = __shfl(scum, (int)mid, 64) > hi;
+            up = le ? mid : up;
+            lo = le ? lo : (mid + 1u > 63u ? 63u : mid + 1u);
+        }
+        uint32_t sbefore = __shfl(sexcl, (int)lo, 64), seg = kSpl * lo;
+        bool found = false;
+#pragma unroll
+        for (int j = 0; j < kSpl; j++) {
+            const uint32_t v = __shfl(sc[j], (int)lo, 64);
+            if (!found) {
+                if (sbefore + v > hi) {
+                    found = true;
+                    seg = kSpl * lo + j;
+                } else {
+                    sbefore += v;
+                }
+            }
+        }
+        const bool hok = hv && found && seg < a.n_segs && hi - sbefore < a.seg_cap;
+        const uint2 hrec =
+            hok ? reinterpret_cast<const uint2*>(a.heads)[(uint64_t)seg * a.seg_cap + (hi - sbefore)] : make_uint2(0u, 0u);
+        const uint64_t ent = hok ? a.table[hrec.x] : 0ull;
+        const uint32_t key = (uint32_t)(ent >> 32) - 1u;  // the page
+        const bool pok = hok && ent != 0ull && key < a.n_pages;
+        const uint32_t chunk = pok ? key / a.pages_per_chunk : 0u;
+        const uint32_t q = pok ? key - chunk * a.pages_per_chunk : 0u;  // the page within its chunk
+        const uint32_t slot = pok ? a.snap_slot[chunk] : 0xFFFFFFFFu;
+        const bool has = pok && slot < a.n_slots;  // CC_NO_SNAPSHOT and any slot out of range: written in place
+        uint32_t* word = a.snap_bitmap + ((uint64_t)(has ? slot : 0u) * a.words_per_slot + (q >> 5));
+        const uint32_t bit = 1u << (q & 31u);
+        bool need = false;
+        if (has) need = !(*word & bit);  // a set bit: the snapshot keeps its first version
+        const uint64_t sidx = need ? (uint64_t)slot * a.pages_per_chunk + q : 0ull;  // page of d_snap / entry of d_snap_crcs
+        uint32_t oc = 0;
+        if (need) {
+            oc = a.page_crcs[key];
+            a.snap_crcs[sidx] = oc;  // moved, not recomputed
+            atomicOr(word, bit);
+        }
+        uint64_t todo = __ballot(need);
+        ncopied += (uint32_t)__popcll(todo);
+        while (todo) {
+            // two pages in flight: both loads, then both stores
+            const uint32_t b0 = (uint32_t)__builtin_ctzll(todo);
+            todo &= todo - 1ull;
+            const bool two = todo != 0ull;
+            const uint32_t b1 = two ? (uint32_t)__builtin_ctzll(todo) : b0;
+            todo &= todo - 1ull;  // (0 stays 0)
+            const uint32_t p0 = __builtin_amdgcn_readlane(key, b0), p1 = __builtin_amdgcn_readlane(key, b1);
+            const uint64_t d0 = readlane64(sidx, b0), d1 = readlane64(sidx, b1);
+            uint32_t w0[M], w1[M];
+            load_page<M>(w0, reinterpret_cast<const uint32_t*>(a.pool + (uint64_t)p0 * pb) + lane);
+            load_page<M>(w1, reinterpret_cast<const uint32_t*>(a.pool + (uint64_t)p1 * pb) + lane);
+            uint32_t* o0 = reinterpret_cast<uint32_t*>(a.snap + d0 * pb) + lane;
+            uint32_t* o1 = reinterpret_cast<uint32_t*>(a.snap + d1 * pb) + lane;
+#pragma unroll
+            for (int j = 0; j < M; j++) __builtin_nontemporal_store(w0[j], o0 + 64 * j);
+            if (two) {
+#pragma unroll
+                for (int j = 0; j < M; j++) __builtin_nontemporal_store(w1[j], o1 + 64 * j);
+            }
+            if constexpr (Verify) {
+                const uint32_t e0 = __builtin_amdgcn_readlane(oc, b0), e1 = __builtin_amdgcn_readlane(oc, b1);
+                const uint32_t r0 = wave_xor(apply_fin(tab, chain<M>(tab, w0, c0, c1), cf)) ^ a.kconst;
+                nstale += r0 != e0 ? 1u : 0u;
+                if (two) {
+                    const uint32_t r1 = wave_xor(apply_fin(tab, chain<M>(tab, w1, c0, c1), cf)) ^ a.kconst;
+                    nstale += r1 != e1 ? 1u : 0u;
+                }
+            }
+        }
+    }
+    if (lane == 0) {
+        if (a.copied && ncopied) atomicAdd(a.copied, (unsigned long long)ncopied);
+        if (Verify && nstale) atomicAdd(a.stale, (unsigned long long)nstale);
+    }
+}
+
 // A small log (<= 64 writes of <= one page each: at most 2 pieces a write) in
 // ONE launch, for the per-request latency of the write path: no table memset,
 // no insert.  Every wave loads the log into its lanes and finds the distinct
@@ -2369,6 +2507,28 @@ hipError_t launch_log_pages(const LogLaunch& a, hipStream_t s) {
         default: return hipErrorInvalidValue;
     }
 #undef CC_GCASE
+    return hipGetLastError();
+}
+
+hipError_t launch_log_cow(const LogCowLaunch& a, hipStream_t s) {
+    if (a.n_segs == 0 || a.n_segs > kInsertBlocks || a.blocks <= 0) return hipErrorInvalidValue;
+#define CC_WCASE(MM)                                                                                          \
+    case MM:                                                                                                  \
+        if (a.stale)                                                                                          \
+            hipLaunchKernelGGL((log_cow_kernel<MM, true>), dim3(a.blocks), dim3(64 * kCowWaves), 0, s, a);    \
+        else                                                                                                  \
+            hipLaunchKernelGGL((log_cow_kernel<MM, false>), dim3(a.blocks), dim3(64 * kCowWaves), 0, s, a);   \
+        break;
+    switch (a.page_bytes / kWaveBytes) {
+        CC_WCASE(1)
+        CC_WCASE(2)
+        CC_WCASE(4)
+        CC_WCASE(8)
+        CC_WCASE(16)
+        CC_WCASE(32)
+        default: return hipErrorInvalidValue;
+    }
+#undef CC_WCASE
     return hipGetLastError();
 }
 

@@ -292,6 +292,64 @@ int cc_apply_log_delta_dev(void* d_pool, uint64_t pool_bytes, uint32_t page_byte
                            const cc_update* d_log, uint64_t n_updates, uint32_t max_len, uint32_t* d_page_crcs,
                            void* d_work, uint64_t work_bytes, void* stream);
 
+/* Copy on write for chunks with an open snapshot: the step CSChunkFile::Write
+ * runs between its sn update and writeData (needCow(sn), then
+ * copy2Snapshot(offset, length): chunkserver_chunkfile.cpp:381-396, :848-884,
+ * :912-963), one page being one block.  Before the batch's writes land, every
+ * page the log touches (a page that gets at least one piece: an entry that
+ * breaks the contract gets none and copies nothing) whose chunk has a snapshot
+ * slot below n_slots and whose bit in that slot's bitmap is clear has its old
+ * bytes copied into the slot at the same chunk offset, d_page_crcs[p] MOVED
+ * (not recomputed) to d_snap_crcs, and its bit set.  A page whose bit is set is
+ * left alone: the snapshot keeps the first version, as Divide(...,
+ * &uncopiedRange, nullptr) does.  A slot index >= n_slots is CC_NO_SNAPSHOT:
+ * nothing is ever written outside d_snap.  Then the batch is applied exactly as
+ * cc_apply_log_dev (delta = 0) or cc_apply_log_delta_dev (delta != 0) applies
+ * it: the pool bytes and d_page_crcs are theirs, bit for bit; cow == NULL IS
+ * that call.  One more launch between the two (three in all; a log of <= 64
+ * entries takes them too: the one-launch path keeps no touched-page list).
+ *
+ * The struct is a HOST struct of device pointers, like cc_pool_shard.  In full
+ * mode too, d_page_crcs is an INPUT for the copied pages (as it always is in
+ * delta mode): it must hold the CRCs of the pages before the batch.
+ *
+ * needCow is decided per request in the reference; here per chunk per CALL:
+ * d_snap_slot is read once, before any write of the batch.  The caller splits
+ * a batch at the request that creates a snapshot (a rare event: one per chunk
+ * per volume snapshot).
+ *
+ * d_stale, when non-NULL, is the optional check: the pass also rehashes every
+ * page it copies and counts those whose bytes disagree with their stored CRC.
+ * Such a page is still copied with its stored CRC, so the mismatch survives in
+ * the snapshot (delta mode's rule for latent corruption).  With d_stale NULL
+ * the pass does no CRC work at all.
+ *
+ * Checked before a device is needed (CC_EINVAL): chunk_bytes a multiple of
+ * page_bytes that divides pool_bytes; every pointer but the two counters
+ * non-NULL; d_snap 4-byte aligned.
+ *
+ * Not covered: the queue (cc_apply_logs_dev groups batch k+1 in batch k's page
+ * kernel, which leaves no boundary for the pass: take one call per batch while
+ * a snapshot is open); verify-on-read of snapshot reads (ReadSpecifiedChunk,
+ * chunkserver_chunkfile.cpp:550-640); clone chunks and Paste. */
+#define CC_NO_SNAPSHOT 0xFFFFFFFFu
+typedef struct cc_cow {
+    uint32_t chunk_bytes;         /* a multiple of page_bytes; pool_bytes a multiple of it */
+    uint32_t n_slots;             /* snapshot slots behind d_snap */
+    const uint32_t* d_snap_slot;  /* [pool_bytes / chunk_bytes] slot of chunk c's open snapshot, or
+                                     CC_NO_SNAPSHOT (needCow false: written in place) */
+    void* d_snap;                 /* n_slots x chunk_bytes; slot s holds the copied pages at their chunk offsets */
+    uint32_t* d_snap_crcs;        /* n_slots x pages_per_chunk */
+    uint32_t* d_snap_bitmap;      /* n_slots x ceil(pages_per_chunk / 32) words; page q of a slot is bit q % 32 of
+                                     word q / 32 = bit q % 8 of byte q / 8 (common/bitmap.h:196-199): the bytes
+                                     of a slot ARE SnapshotMetaPage's bitmap (cc_snap_meta_encode) */
+    uint64_t* d_copied;           /* optional: += pages copied by the call */
+    uint64_t* d_stale;            /* optional: += copied pages whose bytes did not match d_page_crcs */
+} cc_cow;
+int cc_apply_log_cow_dev(void* d_pool, uint64_t pool_bytes, uint32_t page_bytes, const void* d_src,
+                         const cc_update* d_log, uint64_t n_updates, uint32_t max_len, uint32_t* d_page_crcs,
+                         void* d_work, uint64_t work_bytes, void* stream, int delta, const cc_cow* cow);
+
 /* A QUEUE of write logs applied in order, as n_batches cc_apply_log_dev calls
  * (delta = 0) or cc_apply_log_delta_dev calls (delta = 1) would be on `stream`:
  * the same pool bytes and page CRCs, bit for bit.  Pipelined: the page kernel
@@ -551,6 +609,19 @@ int cc_pcrc_decode(const void* buf, uint64_t bytes, cc_pcrc_header* h, uint32_t*
  * (chunkserver_chunkfile.cpp:90-130: header CRC, version 1 or 2), bounds-checked;
  * CC_ECORRUPT otherwise. */
 int cc_chunk_meta_sn(const void* metapage, uint32_t bytes, uint64_t* sn);
+
+/* The snapshot file's metapage, byte for byte SnapshotMetaPage::encode/decode
+ * (datastore/chunkserver_snapshot.cpp:30-82): version u8 = FORMAT_VERSION (1) |
+ * damaged u8 | sn u64 | bits u32 | bitmap (bits + 7) / 8 bytes | CRC32C of
+ * everything before it, u32 | the rest of the page zero.  `bitmap` is a slot of
+ * cc_cow::d_snap_bitmap copied to the host, unchanged (bit q of the slot = bit
+ * q % 8 of byte q / 8).  Bounds-checked: 14 + (bits + 7) / 8 + 4 must fit the
+ * page -- CC_EINVAL on encode, CC_ECORRUPT on decode, as are a bad CRC or
+ * version.  decode: sn / damaged / bits / bitmap may each be NULL; a non-NULL
+ * bitmap of fewer than (bits + 7) / 8 bytes is CC_EINVAL. */
+int cc_snap_meta_encode(uint64_t sn, int damaged, uint32_t bits, const void* bitmap, void* out, uint32_t out_bytes);
+int cc_snap_meta_decode(const void* buf, uint32_t bytes, uint64_t* sn, int* damaged, uint32_t* bits,
+                        void* bitmap, uint32_t bitmap_cap_bytes);
 
 /* Write the table of chunk file `chunk_path` (metapage of meta_bytes, then
  * n_pages data pages) to `table_path`, atomically (temp file + fsync + rename),
