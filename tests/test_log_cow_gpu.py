@@ -168,9 +168,9 @@ def random_log(rng, n, pool_bytes, max_len, pb):
 
 @pytest.mark.parametrize("delta", [False, True])
 @pytest.mark.parametrize("n", [1, 64, 65, 3000])
-@pytest.mark.parametrize("pb", [256, 512, 4096, 8192])
+@pytest.mark.parametrize("pb", [256, 512, 2048, 4096, 8192])
 def test_cow_page_sizes_and_log_sizes(dev, oracle, pb, n, delta):
-    """Every M family (1, 2, 16, 32 dwords a lane) x logs of 1 / 64 (would take
+    """Every M family (1, 2, 8, 16, 32 dwords a lane) x logs of 1 / 64 (would take
     the one-launch path without cow) / 65 / 3,000 writes (several head segments)
     x full and delta mode, on 8 chunks of 40 pages with slots {0, none, 2, none,
     1, out of range, none, 3} and four bits held before the call."""
@@ -244,7 +244,7 @@ def test_cow_hot_pages_and_contract_breakers(dev, oracle, delta):
 
 @pytest.mark.parametrize("verify", [True, False])
 @pytest.mark.parametrize("delta", [False, True])
-@pytest.mark.parametrize("pb", [256, 4096, 8192])
+@pytest.mark.parametrize("pb", [256, 2048, 4096, 8192])
 def test_cow_stale_pages(dev, oracle, pb, delta, verify):
     """Three pages the batch touches and two it does not are corrupted behind
     the CRC table: d_stale comes back 3, the three copies keep mismatching the
