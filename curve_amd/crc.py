@@ -776,6 +776,73 @@ def verify_reads(pool, page_crcs, offsets, lengths, page_bytes: int = PAGE_SIZE,
     return bad, total
 
 
+def _record_cow(cow, stream):
+    for t in (cow.snap_slot, cow.snap, cow.snap_crcs, cow.bitmap):
+        t.record_stream(stream)
+
+
+def read_snap_records(pool, page_crcs, d_reads, n_reads: int, cow: Optional[Cow], bad, total, out=None, out_off=None,
+                      page_bytes: int = PAGE_SIZE, stream=None):
+    """cc_read_snap_dev on a batch already resident on the device: `d_reads` =
+    int64 device tensor of n_reads page-aligned (offset, length) pairs, read
+    through the snapshot view of `cow` (None: the live pool).  Every page is
+    rehashed against the CRC of its source; mismatches are ADDED to `bad`
+    (int32 [n_reads], -1 marks an invalid read) and `total` (int64 [1]).  With
+    `out` (uint8 device tensor) and `out_off` (int64 [n_reads]) read i's bytes
+    land at out[out_off[i]:]; out=None verifies only.  No host sync."""
+    torch = _torch()
+    cs = cow.struct() if cow is not None else None
+    with torch.cuda.device(pool.device):
+        check(lib().cc_read_snap_dev(_dev_ptr(pool, "pool"), _nbytes(pool), page_bytes, _dev_ptr(d_reads, "reads"),
+                                     n_reads, _dev_ptr(page_crcs, "page_crcs"),
+                                     ctypes.byref(cs) if cs is not None else None,
+                                     _dev_ptr(out, "out") if out is not None else None,
+                                     _dev_ptr(out_off, "out_off") if out_off is not None else None,
+                                     _nbytes(out) if out is not None else 0, _dev_ptr(bad, "bad"),
+                                     _dev_ptr(total, "total"), _stream_handle(stream)), "cc_read_snap_dev")
+    if stream is not None and cow is not None:
+        _record_cow(cow, stream)
+
+
+def read_snap(pool, page_crcs, offsets, lengths, cow: Optional[Cow], page_bytes: int = PAGE_SIZE, stream=None,
+              copy: bool = True):
+    """cc_read_snap_dev: the page-aligned reads (offsets, lengths) of the pool
+    as its chunks were when their snapshots in `cow` were taken (cow=None: as
+    they are), every page verified against the CRC of the table it came from.
+    Returns (out, bad_per_read, bad_total): `out` holds the reads' bytes back to
+    back in read order (uint8 device tensor; None with copy=False), the counts
+    are as verify_reads returns them (-1 = invalid read).  No host sync."""
+    import numpy as np
+    torch = _torch()
+    off = np.asarray(offsets, dtype=np.uint64)
+    ln = np.asarray(lengths, dtype=np.uint64)
+    if off.size != ln.size:
+        raise CurveCrcError(_lib.CC_EINVAL, "offsets/lengths size mismatch")
+    n = off.size
+    with _on_stream(stream):
+        bad = torch.zeros(max(n, 1), dtype=torch.int32, device=pool.device)
+        total = torch.zeros(1, dtype=torch.int64, device=pool.device)
+        out = out_off = None
+        if copy:
+            ends = np.cumsum(ln, dtype=np.uint64)
+            out = torch.empty(int(ends[-1]) if n else 0, dtype=torch.uint8, device=pool.device)
+            out_off = torch.from_numpy((ends - ln).view(np.int64)).to(pool.device)
+        if n == 0:
+            return out, bad[:0], total
+        rng = torch.from_numpy(np.stack([off, ln], axis=1).reshape(-1).view(np.int64)).to(pool.device)
+    buf = out
+    if copy and out.numel() == 0:  # nothing but empty reads: a buffer nobody writes keeps the pointer non-NULL
+        with _on_stream(stream):
+            buf = torch.empty(4, dtype=torch.uint8, device=pool.device)
+    read_snap_records(pool, page_crcs, rng, n, cow, bad, total, out=buf, out_off=out_off, page_bytes=page_bytes,
+                      stream=stream)
+    if stream is not None:
+        for t in (rng, buf, out_off):
+            if t is not None:
+                t.record_stream(stream)
+    return out, bad[:n], total
+
+
 def scan_files(paths, chunk_bytes: int = CHUNK_SIZE, meta_bytes: int = META_PAGE_SIZE,
                page_bytes: int = PAGE_SIZE, slice_bytes: int = SCAN_SIZE, io_threads: int = 0):
     """cc_scan_files: native pread + scan of chunk files.

@@ -270,6 +270,32 @@ struct ReadVerifyLaunch {
 hipError_t launch_read_verify(const ReadVerifyLaunch& a, hipStream_t s);
 // <= 64 reads in one launch (no tiles; pages split over waves)
 hipError_t launch_read_verify_small(const ReadVerifyLaunch& a, hipStream_t s);
+// Snapshot reads (cc_read_snap_dev): verify-on-read's schedule over page-aligned
+// reads, every page slot resolved to its snapshot-view source first -- the
+// chunk's slot page and its CRC in snap_crcs when the slot's bitmap holds the
+// page, the live page and page_crcs otherwise -- rehashed against that CRC and,
+// with `out`, stored at out + out_off[read] + (page's position in the read).
+// n_slots == 0: no snapshot (cow == NULL), every page is live and the snapshot
+// fields are not read.
+struct SnapReadLaunch {
+    ReadVerifyLaunch rv;         // pool, reads, page_crcs, counters, tiles, tail, epoch, image, grid
+    uint32_t pages_per_chunk;
+    uint32_t words_per_slot;     // bitmap words a slot: ceil(pages_per_chunk / 32)
+    uint32_t n_slots;
+    uint32_t ppc_mlo, ppc_mhi;   // ceil(2^64 / pages_per_chunk): page / pages_per_chunk for pages < 2^32 (snap_recip)
+    const uint32_t* snap_slot;   // [chunks] slot of the chunk's open snapshot (>= n_slots: none)
+    const unsigned char* snap;   // n_slots x chunk
+    const uint32_t* snap_crcs;   // n_slots x pages_per_chunk
+    const uint32_t* snap_bitmap; // n_slots x words_per_slot
+    unsigned char* out;          // null: verify only
+    const uint64_t* out_off;     // [n_reads] byte offset of read i's bytes in out
+    uint64_t out_bytes;
+};
+// the reciprocal the kernels divide by: ceil(2^64 / d), exact for n < 2^32 (d >= 2; the kernels divide otherwise)
+inline uint64_t snap_recip(uint32_t d) { return d > 1 ? ~0ull / d + 1 : 0; }
+hipError_t launch_snap_read(const SnapReadLaunch& a, hipStream_t s);
+// <= 64 reads in one launch (no tiles, no scratch)
+hipError_t launch_snap_read_small(const SnapReadLaunch& a, hipStream_t s);
 // CRC32C (butil Value) of arbitrary byte ranges of one device buffer, on the
 // flat block schedule, ONE launch: range_flat_kernel counts the
 // 4 KiB blocks of kRangeTiles contiguous tiles of the batch itself (epoch-tagged

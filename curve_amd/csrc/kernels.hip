@@ -2323,6 +2323,340 @@ __global__ __launch_bounds__(64 * kRvWaves) void read_verify_small_kernel(ReadVe
     }
 }
 
+// ---------------------------------------------------------------------------
+// Snapshot reads (cc_read_snap_dev): verify-on-read's schedule, every page
+// slot resolved to its snapshot-view source, rehashed against that source's
+// CRC and (Copy) delivered.  Replaces the host loop of
+// CSChunkFile::ReadSpecifiedChunk (chunkserver_chunkfile.cpp:550-636:
+// Divide() into copied and uncopied ranges, readData for one set,
+// snapshot_->Read for the other); with no slots, CSChunkFile::Read (:497-536).
+// ---------------------------------------------------------------------------
+// Pages of a read that is served: 0 for an empty read and for an invalid one
+// (misaligned, past the pool, or -- with an output -- an output range that is
+// unaligned or leaves the buffer), so an invalid read takes no slot.
+template <bool Copy>
+__device__ __forceinline__ bool snap_read_bad(const SnapReadLaunch& a, const RangeDesc& r, uint64_t oo) {
+    if (!r.len) return false;
+    if ((r.off | r.len) & (uint64_t)(a.rv.page_bytes - 1u)) return true;
+    if (r.off >= a.rv.pool_bytes || r.len > a.rv.pool_bytes - r.off) return true;
+    return Copy && ((oo & 3u) || oo > a.out_bytes || r.len > a.out_bytes - oo);
+}
+template <bool Copy>
+__device__ __forceinline__ uint64_t snap_pages(const SnapReadLaunch& a, const RangeDesc& r, uint64_t oo) {
+    return snap_read_bad<Copy>(a, r, oo) ? 0u : read_pages(a.rv, r);
+}
+
+// Pages of tile t, uniform; mark: invalid reads get bad_per_read = UINT32_MAX
+// (the tile's counting wave marks them, as read_tile_count does).
+template <bool Copy>
+__device__ __forceinline__ uint64_t snap_tile_count(const SnapReadLaunch& a, uint32_t t, uint32_t lane, bool mark) {
+    const uint64_t lo = a.rv.n_reads * t / kReadTiles, hi = a.rv.n_reads * (t + 1) / kReadTiles;
+    uint64_t sum = 0;
+    for (uint64_t i = lo + lane; i < hi; i += 64) {
+        const RangeDesc r = a.rv.reads[i];
+        const uint64_t oo = Copy ? a.out_off[i] : 0u;
+        const bool bad = snap_read_bad<Copy>(a, r, oo);
+        sum += bad ? 0u : read_pages(a.rv, r);
+        if (mark && bad) a.rv.bad_per_read[i] = 0xFFFFFFFFu;
+    }
+#pragma unroll
+    for (int d = 32; d; d >>= 1) sum += __shfl_xor(sum, d, 64);
+    return sum;
+}
+
+// One page slot on its way to its loads.  Its position is uniform (SGPRs);
+// the source is resolved in three stages a step apart: snap_slot_of (chunk,
+// page in chunk, the chunk's slot), snap_word_of (the slot's bitmap word),
+// snap_source (data and CRC address).  The two table words come in with VECTOR
+// loads (the opaque zero: a scalar load would share lgkmcnt with the chain's
+// LDS lookups) and stay in a VGPR, the same value in every lane, until the
+// next stage takes them with a readfirstlane a step later -- the wait sits
+// there, a whole page's hash after the load, not at the load.
+struct SnapPg {
+    uint64_t g;      // pool page
+    uint32_t owner;  // lane holding the page's read
+    uint32_t rel;    // the page's position in its read
+    uint32_t q;      // page in chunk
+    uint32_t s;      // the chunk's slot (>= n_slots: none), once snap_word_of has taken it
+    uint32_t sv;     // VGPR: the slot as loaded
+    uint32_t wv;     // VGPR: the slot's bitmap word holding bit q, as loaded
+};
+__device__ __forceinline__ void snap_slot_of(const SnapReadLaunch& a, SnapPg& p, uint32_t vz) {
+    p.q = 0;
+    p.s = 0xFFFFFFFFu;
+    p.sv = 0xFFFFFFFFu;
+    p.wv = 0;
+    if (!a.n_slots) return;  // uniform: no snapshot, nothing to resolve
+    uint64_t c;
+    if ((p.g >> 32) || a.pages_per_chunk == 1) {  // beyond the reciprocal's range (uniform, rare)
+        c = p.g / a.pages_per_chunk;
+    } else {
+        const uint32_t g32 = (uint32_t)p.g;
+        c = ((uint64_t)g32 * a.ppc_mhi + ((uint64_t)g32 * a.ppc_mlo >> 32)) >> 32;
+    }
+    p.q = (uint32_t)(p.g - c * a.pages_per_chunk);
+    p.sv = a.snap_slot[c + vz];
+}
+__device__ __forceinline__ void snap_word_of(const SnapReadLaunch& a, SnapPg& p, uint32_t vz) {
+    if (!a.n_slots) return;
+    p.s = __builtin_amdgcn_readfirstlane(p.sv);
+    const uint32_t sc = p.s < a.n_slots ? p.s : 0u;  // clamped: the same load every page
+    p.wv = a.snap_bitmap[(uint64_t)sc * a.words_per_slot + (p.q >> 5) + vz];
+}
+struct SnapSrc {
+    const uint32_t* data;
+    const uint32_t* crc;
+};
+__device__ __forceinline__ SnapSrc snap_source(const SnapReadLaunch& a, const SnapPg& p) {
+    SnapSrc r;
+    r.data = reinterpret_cast<const uint32_t*>(reinterpret_cast<const unsigned char*>(a.rv.pool) +
+                                               (p.g << a.rv.page_shift));
+    r.crc = a.rv.page_crcs + p.g;
+    if (!a.n_slots) return r;
+    const uint32_t word = __builtin_amdgcn_readfirstlane(p.wv);
+    if (p.s < a.n_slots && ((word >> (p.q & 31u)) & 1u)) {
+        const uint64_t sp = (uint64_t)p.s * a.pages_per_chunk + p.q;
+        r.data = reinterpret_cast<const uint32_t*>(a.snap + (sp << a.rv.page_shift));
+        r.crc = a.snap_crcs + sp;
+    }
+    return r;
+}
+
+// load_page's layout back out: M coalesced 256-byte rows (nt: written once, read by the caller later)
+template <int M>
+__device__ __forceinline__ void store_page(const uint32_t (&w)[M], uint32_t* p) {
+#pragma unroll
+    for (int j = 0; j < M; j++) __builtin_nontemporal_store(w[j], p + 64 * j);
+}
+
+// read_verify_kernel's schedule (tile counts published by the waves, shares at
+// page granularity, 1/16 dynamic tail, three register sets rotating) with the
+// per-page source resolution: the step that hashes page k first takes the
+// table words loaded a step earlier, issues page k+3's bitmap-word load and
+// page k+4's slot load, and then page k+2's loads from the source just
+// resolved.  The table loads go BEFORE the page's: vmcnt retires in order, so a
+// table word issued after a page's loads would hold the step that needs it
+// until that page had landed, a page early.  Lane j of a group of 64 reads
+// also holds its read's output offset; a page's output address is the owner
+// lane's offset (readlane) plus its position in the read.
+template <int M, bool Copy>
+__global__ __launch_bounds__(64 * kRvWaves) void snap_read_kernel(SnapReadLaunch a) {
+    __shared__ uint32_t tab[kLdsBytes / 4];
+    const uint64_t n = a.rv.n_reads;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint64_t Wg = (uint64_t)gridDim.x * kRvWaves;
+    const uint64_t w = (uint64_t)blockIdx.x * kRvWaves + wave;
+    const uint64_t tag = (uint64_t)a.rv.epoch << kEpochShift;
+    for (uint64_t t = w; t < kReadTiles; t += Wg) {
+        const uint64_t cnt = snap_tile_count<Copy>(a, (uint32_t)t, lane, true);
+        if (lane == 0) __hip_atomic_store(a.rv.tiles + t, tag | cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    unsigned long long* dyn_ctr = a.rv.tail + (a.rv.epoch & 1u) * kDynCtrWords64;
+    if (blockIdx.x == 0 && threadIdx.x < kRvHeads)
+        atomicExch(a.rv.tail + ((a.rv.epoch + 1u) & 1u) * kDynCtrWords64 + threadIdx.x * kDynHeadStride, 0ull);
+    fill_lds<64 * kRvWaves>(tab, static_cast<const uint4*>(a.rv.image));
+    const uint32_t c0 = lane << 2 & 0x7Cu;
+    const uint32_t c1 = c0 | 0x10000u;
+    const uint32_t cf = kFinBase + (lane << 2);
+    uint32_t vz = 0;
+    asm volatile("" : "+v"(vz));  // opaque zero: keeps uniform-address loads on the vector path
+
+    constexpr int kTpl = kReadTiles / 64;
+    uint64_t tb[kTpl];
+    wait_tiles<kTpl>(tb, a.rv.tiles, tag, lane, [&](uint32_t t) { return snap_tile_count<Copy>(a, t, lane, false); });
+    uint64_t lsum = 0;
+#pragma unroll
+    for (int j = 0; j < kTpl; j++) lsum += tb[j];
+    const uint64_t cum = wave_scan_incl(lsum, lane);
+    const uint64_t T = readlane64(cum, 63);
+    const uint64_t Wt = (T + kRvMinSlots - 1) / kRvMinSlots;
+    const uint64_t W = Wt < Wg ? (Wt ? Wt : 1) : Wg;
+    if ((uint64_t)blockIdx.x * kRvWaves >= W) return;  // uniform per block: no share, no tail
+    const uint64_t Ts = T - T / kRvDynDiv;
+    uint32_t dyn_head, dyn_tried;
+    tail_cursor<kRvHeads>(dyn_head, dyn_tried);
+    uint64_t lo_slot = w < W ? Ts * w / W : Ts, hi_slot = w < W ? Ts * (w + 1) / W : Ts;  // waves past W: tail only
+#pragma unroll 1
+    for (;;) {
+        uint64_t base = n, S = 0;
+        RangeDesc rs;
+        uint64_t os = 0;
+        bool have_rs = false;
+        if (lo_slot < hi_slot) {
+            const TileHit th = tile_of(cum, tb, lo_slot, lane);
+            base = n * th.tile / kReadTiles;
+            S = th.before;
+            for (;;) {
+                const uint64_t ri = base + lane;
+                rs = a.rv.reads[(ri < n ? ri : base) + vz];
+                os = Copy ? a.out_off[(ri < n ? ri : base) + vz] : 0u;
+                const uint64_t c = wave_scan_incl(ri < n ? snap_pages<Copy>(a, rs, os) : 0u, lane);
+                const uint64_t tot = readlane64(c, 63);
+                if (S + tot > lo_slot || base + 64 >= n) break;
+                S += tot;
+                base += 64;
+            }
+            have_rs = true;
+        }
+        for (; base < n && S < hi_slot; base += 64) {
+            const uint64_t ri = base + lane;
+            const bool valid = ri < n;
+            const RangeDesc r = have_rs ? rs : a.rv.reads[(valid ? ri : base) + vz];
+            const uint64_t oo = !Copy ? 0u : have_rs ? os : a.out_off[(valid ? ri : base) + vz];
+            have_rs = false;
+            const uint32_t cnt = valid ? (uint32_t)snap_pages<Copy>(a, r, oo) : 0u;  // 0 also for invalid reads
+            const uint64_t p0 = r.off >> a.rv.page_shift;
+            uint32_t cum32 = cnt;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const uint32_t o = __shfl_up(cum32, d, 64);
+                if (lane >= (uint32_t)d) cum32 += o;
+            }
+            const uint32_t P = __builtin_amdgcn_readlane(cum32, 63);
+            const uint32_t ks = lo_slot > S ? (uint32_t)(lo_slot - S) : 0u;
+            const uint32_t ke = hi_slot - S < (uint64_t)P ? (uint32_t)(hi_slot - S) : P;
+            S += P;
+            if (ks >= ke) continue;
+            // slot k (clamped to the share's last): its read's lane, its page, its source's chunk slot
+            auto locate = [&](uint32_t k) {
+                k = k < ke ? k : ke - 1;
+                SnapPg p;
+                p.owner = (uint32_t)__builtin_ctzll(__ballot(cum32 > k));
+                const uint32_t before = p.owner ? (uint32_t)__builtin_amdgcn_readlane(cum32, p.owner - 1) : 0u;
+                p.rel = k - before;
+                p.g = readlane64(p0, p.owner) + p.rel;
+                snap_slot_of(a, p, vz);
+                return p;
+            };
+            // the resolved page's stored CRC, output offset and loads; then the
+            // page behind it moves up: its bitmap word, and the slot of the one after
+            SnapPg p3, p4;
+            auto issue = [&](uint32_t kn, uint32_t (&Y)[M], uint32_t& sy, uint32_t& oy, uint64_t& dy) {
+                const SnapSrc src = snap_source(a, p3);
+                oy = p3.owner;
+                dy = Copy ? readlane64(oo, p3.owner) + ((uint64_t)p3.rel << a.rv.page_shift) : 0u;
+                p3 = p4;
+                snap_word_of(a, p3, vz);
+                p4 = locate(kn);
+                __builtin_amdgcn_sched_barrier(0);  // the table loads stay ahead of the page's
+                sy = src.crc[vz];
+                load_page<M>(Y, src.data + lane);
+            };
+            uint32_t A[M], B[M], Cq[M];
+            uint32_t sA, sB, sC, oA, oB, oC;
+            uint64_t dA, dB, dC;
+            p3 = locate(ks);
+            snap_word_of(a, p3, vz);
+            p4 = locate(ks + 1);
+            issue(ks + 2, A, sA, oA, dA);
+            issue(ks + 3, B, sB, oB, dB);
+            sC = sB, oC = oB, dC = dB;
+            // hash X (page k: stored CRC sx, owner lane ox, output offset dx); page k+2's loads go into Y
+            auto step = [&](uint32_t (&X)[M], uint32_t sx, uint32_t ox, uint64_t dx, uint32_t k, uint32_t (&Y)[M],
+                            uint32_t& sy, uint32_t& oy, uint64_t& dy) {
+                const bool more = k + 1 < ke;
+                issue(k + 4, Y, sy, oy, dy);
+                const uint32_t crc = wave_xor(apply_fin(tab, chain<M>(tab, X, c0, c1), cf)) ^ a.rv.kconst;
+                if (Copy) store_page<M>(X, reinterpret_cast<uint32_t*>(a.out + dx) + lane);
+                if (crc != sx && lane == 0) {
+                    atomicAdd(a.rv.bad_per_read + base + ox, 1u);
+                    atomicAdd(a.rv.bad_total, 1ull);
+                }
+                return more;
+            };
+            for (uint32_t k = ks;; k += 3) {
+                if (!step(A, sA, oA, dA, k, Cq, sC, oC, dC)) break;
+                if (!step(B, sB, oB, dB, k + 1, A, sA, oA, dA)) break;
+                if (!step(Cq, sC, oC, dC, k + 2, B, sB, oB, dB)) break;
+            }
+        }
+        const uint64_t n_dyn = (T - Ts + kRvDynSlots - 1) / kRvDynSlots;
+        const uint64_t c = tail_pull<kRvHeads>(dyn_ctr, n_dyn, dyn_head, dyn_tried, lane);
+        if (c >= n_dyn) break;
+        lo_slot = Ts + c * kRvDynSlots;
+        hi_slot = lo_slot + kRvDynSlots < T ? lo_slot + kRvDynSlots : T;
+    }
+}
+
+// <= 64 reads (one per lane) in ONE launch with no scratch, as
+// read_verify_small_kernel: every wave works out the batch's pages per read
+// (wave 0 of block 0 marks the invalid ones), the P pages are split evenly over
+// the fewest waves that give each >= kRvSmallMinSlots, and a wave resolves the
+// next page's source while it hashes one.
+template <int M, bool Copy>
+__global__ __launch_bounds__(64 * kRvWaves) void snap_read_small_kernel(SnapReadLaunch a) {
+    __shared__ uint32_t tab[kLdsBytes / 4];
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    uint32_t vz = 0;
+    asm volatile("" : "+v"(vz));
+    const bool valid = lane < a.rv.n_reads;
+    const RangeDesc r = a.rv.reads[(valid ? lane : 0u) + vz];
+    const uint64_t oo = Copy ? a.out_off[(valid ? lane : 0u) + vz] : 0u;
+    const bool bad = snap_read_bad<Copy>(a, r, oo);
+    const uint32_t cnt = valid && !bad ? (uint32_t)read_pages(a.rv, r) : 0u;
+    if (valid && bad && blockIdx.x == 0 && wave == 0) a.rv.bad_per_read[lane] = 0xFFFFFFFFu;
+    const uint64_t p0 = r.off >> a.rv.page_shift;
+    uint32_t cum = cnt;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t o = __shfl_up(cum, d, 64);
+        if (lane >= (uint32_t)d) cum += o;
+    }
+    const uint32_t P = __builtin_amdgcn_readlane(cum, 63);
+    const uint32_t Wg = gridDim.x * kRvWaves, Wt = (P + kRvSmallMinSlots - 1) / kRvSmallMinSlots;
+    const uint32_t W = Wt < Wg ? Wt : Wg;
+    if (blockIdx.x * (uint32_t)kRvWaves >= W) return;  // uniform per block (P == 0: every block)
+    fill_lds<64 * kRvWaves>(tab, static_cast<const uint4*>(a.rv.image));
+    const uint32_t w = blockIdx.x * kRvWaves + wave;
+    if (w >= W) return;
+    const uint32_t k0 = (uint32_t)((uint64_t)P * w / W), k1 = (uint32_t)((uint64_t)P * (w + 1) / W);
+    if (k0 >= k1) return;
+    const uint32_t c0 = lane << 2 & 0x7Cu;
+    const uint32_t c1 = c0 | 0x10000u;
+    const uint32_t cf = kFinBase + (lane << 2);
+    auto locate = [&](uint32_t k) {
+        k = k < k1 ? k : k1 - 1;
+        SnapPg p;
+        p.owner = (uint32_t)__builtin_ctzll(__ballot(cum > k));
+        const uint32_t before = p.owner ? (uint32_t)__builtin_amdgcn_readlane(cum, p.owner - 1) : 0u;
+        p.rel = k - before;
+        p.g = readlane64(p0, p.owner) + p.rel;
+        snap_slot_of(a, p, vz);
+        snap_word_of(a, p, vz);
+        return p;
+    };
+    auto issue = [&](const SnapPg& p, uint32_t (&Y)[M], uint32_t& sy, uint32_t& oy, uint64_t& dy) {
+        const SnapSrc src = snap_source(a, p);
+        sy = src.crc[vz];
+        oy = p.owner;
+        dy = Copy ? readlane64(oo, p.owner) + ((uint64_t)p.rel << a.rv.page_shift) : 0u;
+        load_page<M>(Y, src.data + lane);
+    };
+    // pages k0 .. k1-1, the next page's loads in flight while one is hashed
+    uint32_t X[M], Y[M];
+    uint32_t sx, sy, ox, oy;
+    uint64_t dx, dy;
+    issue(locate(k0), X, sx, ox, dx);
+    SnapPg pn = locate(k0 + 1);
+    for (uint32_t k = k0; k < k1; k++) {
+        issue(pn, Y, sy, oy, dy);  // clamped: same loads every step
+        pn = locate(k + 2);
+        const uint32_t crc = wave_xor(apply_fin(tab, chain<M>(tab, X, c0, c1), cf)) ^ a.rv.kconst;
+        if (Copy) store_page<M>(X, reinterpret_cast<uint32_t*>(a.out + dx) + lane);
+        if (crc != sx && lane == 0) {
+            atomicAdd(a.rv.bad_per_read + ox, 1u);
+            atomicAdd(a.rv.bad_total, 1ull);
+        }
+#pragma unroll
+        for (int j = 0; j < M; j++) X[j] = Y[j];
+        sx = sy;
+        ox = oy;
+        dx = dy;
+    }
+}
+
 __global__ void combine_kernel(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b, uint32_t m,
                                uint64_t n, uint32_t* __restrict__ out) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -2591,6 +2925,50 @@ hipError_t launch_read_verify(const ReadVerifyLaunch& a, hipStream_t s) {
 #define CC_RCASE(MM) \
     case MM: hipLaunchKernelGGL((read_verify_kernel<MM>), dim3(a.blocks), dim3(64 * kRvWaves), 0, s, a); break;
     switch (a.page_bytes / kWaveBytes) {
+        CC_RCASE(1)
+        CC_RCASE(2)
+        CC_RCASE(4)
+        CC_RCASE(8)
+        CC_RCASE(16)
+        CC_RCASE(32)
+        default: return hipErrorInvalidValue;
+    }
+#undef CC_RCASE
+    return hipGetLastError();
+}
+
+hipError_t launch_snap_read_small(const SnapReadLaunch& a, hipStream_t s) {
+    if (a.rv.n_reads == 0 || a.rv.n_reads > 64) return hipErrorInvalidValue;
+#define CC_SCASE(MM)                                                                                                  \
+    case MM:                                                                                                          \
+        if (a.out)                                                                                                    \
+            hipLaunchKernelGGL((snap_read_small_kernel<MM, true>), dim3(a.rv.blocks), dim3(64 * kRvWaves), 0, s, a);  \
+        else                                                                                                          \
+            hipLaunchKernelGGL((snap_read_small_kernel<MM, false>), dim3(a.rv.blocks), dim3(64 * kRvWaves), 0, s, a); \
+        break;
+    switch (a.rv.page_bytes / kWaveBytes) {
+        CC_SCASE(1)
+        CC_SCASE(2)
+        CC_SCASE(4)
+        CC_SCASE(8)
+        CC_SCASE(16)
+        CC_SCASE(32)
+        default: return hipErrorInvalidValue;
+    }
+#undef CC_SCASE
+    return hipGetLastError();
+}
+
+hipError_t launch_snap_read(const SnapReadLaunch& a, hipStream_t s) {
+    if (a.rv.n_reads == 0) return hipSuccess;
+#define CC_RCASE(MM)                                                                                            \
+    case MM:                                                                                                    \
+        if (a.out)                                                                                              \
+            hipLaunchKernelGGL((snap_read_kernel<MM, true>), dim3(a.rv.blocks), dim3(64 * kRvWaves), 0, s, a);  \
+        else                                                                                                    \
+            hipLaunchKernelGGL((snap_read_kernel<MM, false>), dim3(a.rv.blocks), dim3(64 * kRvWaves), 0, s, a); \
+        break;
+    switch (a.rv.page_bytes / kWaveBytes) {
         CC_RCASE(1)
         CC_RCASE(2)
         CC_RCASE(4)

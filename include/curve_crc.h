@@ -330,8 +330,8 @@ int cc_apply_log_delta_dev(void* d_pool, uint64_t pool_bytes, uint32_t page_byte
  *
  * Not covered: the queue (cc_apply_logs_dev groups batch k+1 in batch k's page
  * kernel, which leaves no boundary for the pass: take one call per batch while
- * a snapshot is open); verify-on-read of snapshot reads (ReadSpecifiedChunk,
- * chunkserver_chunkfile.cpp:550-640); clone chunks and Paste. */
+ * a snapshot is open); clone chunks and Paste.  (Reading a snapshot back:
+ * cc_read_snap_dev.) */
 #define CC_NO_SNAPSHOT 0xFFFFFFFFu
 typedef struct cc_cow {
     uint32_t chunk_bytes;         /* a multiple of page_bytes; pool_bytes a multiple of it */
@@ -392,6 +392,63 @@ uint64_t cc_verify_reads_work_bytes(uint64_t n_reads);
 int cc_verify_reads_dev(const void* d_pool, uint64_t pool_bytes, uint32_t page_bytes, const cc_range* d_reads,
                         uint64_t n_reads, const uint32_t* d_page_crcs, uint32_t* d_bad_per_read,
                         uint64_t* d_bad_total, void* d_work, uint64_t work_bytes, void* stream);
+
+/* Snapshot reads: a batch of reads of chunks AS THEY WERE when their snapshot
+ * was taken, verified and gathered on the device.  Replaces the host loop of
+ * CSChunkFile::ReadSpecifiedChunk (chunkserver_chunkfile.cpp:550-636:
+ * Divide(begin, end, &uncopied, &copied), then readData for the uncopied
+ * ranges and snapshot_->Read for the copied ones), which returns the bytes
+ * unchecked; with cow == NULL it is a verified, gathering CSChunkFile::Read
+ * (:497-536, the sn == metaPage_.sn branch).
+ *
+ * Reads are pool byte ranges as for cc_verify_reads_dev, but off and len must
+ * be multiples of page_bytes (one page is one block, the COW call's
+ * convention; CheckOffsetAndLength, chunkserver_chunkfile.h:386-394).  A read
+ * may cross chunk boundaries: every page is resolved on its own.  For pool
+ * page p, chunk c = p / pages_per_chunk, page in chunk q = p % pages_per_chunk
+ * and slot s = cow->d_snap_slot[c]: when cow != NULL, s < cow->n_slots and bit
+ * q of slot s's bitmap is set, the page's bytes are d_snap + (s *
+ * pages_per_chunk + q) * page_bytes and its expected CRC d_snap_crcs[s *
+ * pages_per_chunk + q]; otherwise (CC_NO_SNAPSHOT, any slot >= n_slots, a
+ * clear bit, cow == NULL) they are the live pool page and d_page_crcs[p].  A
+ * live page under a set bit is not part of the view: it is neither read nor
+ * checked.  `cow` is the struct cc_apply_log_cow_dev takes; d_copied and
+ * d_stale are ignored and everything is read only.  The caller must not run a
+ * COW batch over the same slots on another stream at the same time.
+ *
+ * Every page of every valid read is rehashed whole and compared with its
+ * expected CRC: d_bad_per_read[i] += the mismatching pages of read i (the
+ * caller zeroes it), *d_bad_total += all mismatches.  With d_out != NULL the
+ * page's bytes are also stored at d_out + d_out_off[i] + (page start - off_i),
+ * whether or not the page matched (the reference returns bytes unchecked; the
+ * counts tell the caller what to do with them).  d_out == NULL verifies only:
+ * d_out_off may be NULL and out_bytes is ignored.  Overlapping output ranges
+ * are the caller's business.
+ *
+ * A read is INVALID -- d_bad_per_read[i] = UINT32_MAX, not hashed, nothing
+ * written -- when its off or len is misaligned, when it runs past the pool
+ * (off >= pool_bytes or len > pool_bytes - off) or, with d_out, when
+ * d_out_off[i] is not 4-byte aligned or d_out_off[i] + len > out_bytes.
+ * Nothing is ever written outside [d_out, d_out + out_bytes).  len == 0 is
+ * valid whatever its off: it touches nothing and leaves its word alone.
+ *
+ * Checked before a device is needed (CC_EINVAL): page_bytes = 256 * 2^k
+ * (k = 0..5); pool_bytes whole pages; d_pool 4-byte aligned; d_pool, d_reads,
+ * d_page_crcs, d_bad_per_read, d_bad_total non-NULL; d_out non-NULL with a
+ * NULL d_out_off or not 4-byte aligned; with cow, chunk_bytes a multiple of
+ * page_bytes that divides pool_bytes, its slot, snap, CRC and bitmap pointers
+ * non-NULL and d_snap 4-byte aligned; n_reads < 2^31.  n_reads == 0 is CC_OK.
+ * No GPU: CC_ENODEV, never a CPU fallback.
+ *
+ * ONE launch on verify-on-read's schedule (every touched page one slot, the
+ * slots split evenly over the device, the last 1/16 dynamically), using the
+ * stream's range scratch the engine keeps (see cc_crc_ranges_dev; shared with
+ * cc_verify_reads_dev, no caller work buffer); a batch of <= 64 reads on a
+ * pool of < 2^26 pages takes one launch with no scratch at all. */
+int cc_read_snap_dev(const void* d_pool, uint64_t pool_bytes, uint32_t page_bytes, const cc_range* d_reads,
+                     uint64_t n_reads, const uint32_t* d_page_crcs, const cc_cow* cow, void* d_out,
+                     const uint64_t* d_out_off, uint64_t out_bytes, uint32_t* d_bad_per_read, uint64_t* d_bad_total,
+                     void* stream);
 
 /* One chunk file as the datastore holds it: metapage + data
  * (file = metapage || data, chunkserver_chunkfile.cpp:497-536). */
