@@ -95,6 +95,16 @@ class CcCow(ctypes.Structure):
 
 CC_NO_SNAPSHOT = 0xFFFFFFFF
 
+
+class CcClone(ctypes.Structure):
+    """cc_clone (include/curve_crc.h): the written-page bitmaps of a pool's clone chunks
+    (a host struct of device pointers)."""
+    _fields_ = [("chunk_bytes", _u32), ("n_slots", _u32), ("d_clone_slot", _vp), ("d_bitmap", _vp),
+                ("d_claim", _vp), ("d_pasted", _vp)]
+
+
+CC_NOT_CLONE = 0xFFFFFFFF
+
 SIGNATURES = {
     "crc32c_value": (_u32, [_vp, _sz]),
     "crc32c_extend": (_u32, [_u32, _vp, _sz]),
@@ -149,6 +159,9 @@ SIGNATURES = {
     "cc_verify_reads_dev": (_int, [_vp, _u64, _u32, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _vp]),
     "cc_read_snap_dev": (_int, [_vp, _u64, _u32, _vp, _u64, _vp, ctypes.POINTER(CcCow), _vp, _vp, _u64, _vp, _vp,
                                 _vp]),
+    "cc_paste_dev": (_int, [_vp, _u64, _u32, _vp, _u64, _vp, _u64, _vp, ctypes.POINTER(CcClone), _vp, _vp]),
+    "cc_clone_mark_dev": (_int, [_u64, _u32, _vp, _u64, _u32, ctypes.POINTER(CcClone), _vp]),
+    "cc_clone_check_reads_dev": (_int, [_u64, _u32, _vp, _u64, ctypes.POINTER(CcClone), _vp, _vp, _vp]),
     "cc_comm_unique_id": (_int, [_vp, _sz]),
     "cc_comm_init": (_int, [ctypes.POINTER(_vp), _int, _int, _vp, _sz]),
     "cc_comm_init_timeout": (_int, [ctypes.POINTER(_vp), _int, _int, _vp, _sz, _u32]),

@@ -89,6 +89,27 @@ class ChunkFileMetaPage:
         return CSErrorCode.Success, m
 
 
+def clone_metapage_after(meta: ChunkFileMetaPage, bitmap: bytes) -> ChunkFileMetaPage:
+    """flush()'s metapage step on a clone chunk (chunkserver_chunkfile.cpp:965-1000):
+    a copy of `meta` carrying `bitmap` (crc.Clone.slot_bitmap_bytes after a paste
+    or a marked write).  Once all bitmap_bits bits are set the chunk is an
+    ordinary one (:972-996): location is emptied and the bitmap dropped, so the
+    encoded page is a non-clone metapage with its CRC at byte 25.  A metapage
+    that is no clone's comes back unchanged."""
+    from dataclasses import replace
+    if not meta.location:
+        return replace(meta)
+    bits = meta.bitmap_bits
+    nbytes = (bits + 7) >> 3
+    bm = (bytes(bitmap) + bytes(nbytes))[:nbytes]
+    written = sum(bin(b).count("1") for b in bm[:bits >> 3])
+    if bits & 7:
+        written += bin(bm[bits >> 3] & ((1 << (bits & 7)) - 1)).count("1")
+    if written == bits:
+        return replace(meta, location=b"", bitmap_bits=0, bitmap=b"")
+    return replace(meta, bitmap=bm)
+
+
 def chunk_file_name(chunk_id: int, snap_sn: Optional[int] = None) -> str:
     return f"chunk_{chunk_id}" if snap_sn is None else f"chunk_{chunk_id}_snap_{snap_sn}"
 

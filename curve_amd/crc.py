@@ -843,6 +843,133 @@ def read_snap(pool, page_crcs, offsets, lengths, cow: Optional[Cow], page_bytes:
     return out, bad[:n], total
 
 
+class Clone:
+    """The written-page bitmaps of a pool's clone chunks (cc_clone,
+    include/curve_crc.h), as device tensors for a pool of `n_chunks` chunks of
+    `chunk_bytes`:
+      clone_slot int32 [n_chunks]   chunk c's bitmap slot, or -1 (CC_NOT_CLONE; the default)
+      bitmap     int32 [n_slots, ceil(pages_per_chunk / 32)]  (a row's bytes are ChunkFileMetaPage's bitmap)
+      claim      int32 [n_slots, pages_per_chunk]  paste's scratch: -1 everywhere between calls
+      pasted     int64 [1]          running count of pasted pages"""
+
+    def __init__(self, n_chunks: int, chunk_bytes: int, page_bytes: int = PAGE_SIZE, n_slots: int = 1, device=None):
+        torch = _torch()
+        if chunk_bytes <= 0 or chunk_bytes % page_bytes:
+            raise CurveCrcError(_lib.CC_EINVAL, "chunk_bytes must be a multiple of page_bytes")
+        dev = device if device is not None else torch.device("cuda", torch.cuda.current_device())
+        self.n_chunks, self.chunk_bytes, self.page_bytes, self.n_slots = n_chunks, chunk_bytes, page_bytes, n_slots
+        self.pages_per_chunk = chunk_bytes // page_bytes
+        self.words_per_slot = (self.pages_per_chunk + 31) // 32
+        self.clone_slot = torch.full((n_chunks,), -1, dtype=torch.int32, device=dev)
+        self.bitmap = torch.zeros((n_slots, self.words_per_slot), dtype=torch.int32, device=dev)
+        self.claim = torch.full((n_slots, self.pages_per_chunk), -1, dtype=torch.int32, device=dev)
+        self.pasted = torch.zeros(1, dtype=torch.int64, device=dev)
+
+    def struct(self) -> "_lib.CcClone":
+        c = _lib.CcClone()
+        c.chunk_bytes, c.n_slots = self.chunk_bytes, self.n_slots
+        c.d_clone_slot = _dev_ptr(self.clone_slot, "clone_slot")
+        c.d_bitmap = _dev_ptr(self.bitmap, "bitmap")
+        c.d_claim = _dev_ptr(self.claim, "claim")
+        c.d_pasted = _dev_ptr(self.pasted, "pasted")
+        return c
+
+    def slot_bitmap_bytes(self, slot: int) -> bytes:
+        """Slot `slot`'s bitmap as ChunkFileMetaPage holds it (chunkfile.clone_metapage_after's `bitmap`)."""
+        return self.bitmap[slot].cpu().numpy().tobytes()[:(self.pages_per_chunk + 7) // 8]
+
+
+def _record_clone(clone, stream):
+    for t in (clone.clone_slot, clone.bitmap, clone.claim, clone.pasted):
+        t.record_stream(stream)
+
+
+def paste_records(pool, page_crcs, src, d_pastes, n: int, clone: Clone, pasted_per_entry, page_bytes: int = PAGE_SIZE,
+                  stream=None):
+    """cc_paste_dev on a batch already resident on the device: `d_pastes` =
+    device tensor of n cc_update records (log_records), an ORDERED batch of
+    Paste requests.  A page of a clone chunk whose bit in `clone` is clear is
+    written once, from the lowest-indexed valid entry covering it, its bit set
+    and its CRC recomputed in `page_crcs`; every other page keeps bytes and CRC.
+    The pages entry i pasted are ADDED to pasted_per_entry[i] (int32 [n], -1
+    marks an invalid entry), all of them to clone.pasted.  No host sync."""
+    torch = _torch()
+    cs = clone.struct()
+    with torch.cuda.device(pool.device):
+        check(lib().cc_paste_dev(_dev_ptr(pool, "pool"), _nbytes(pool), page_bytes, _dev_ptr(src, "src"),
+                                 _nbytes(src), _dev_ptr(d_pastes, "pastes"), n, _dev_ptr(page_crcs, "page_crcs"),
+                                 ctypes.byref(cs), _dev_ptr(pasted_per_entry, "pasted_per_entry"),
+                                 _stream_handle(stream)), "cc_paste_dev")
+    if stream is not None:
+        _record_clone(clone, stream)
+
+
+def paste(pool, page_crcs, src, dst_off, src_off, lens, clone: Clone, page_bytes: int = PAGE_SIZE, stream=None):
+    """cc_paste_dev: the Paste requests (dst_off, src_off, lens), in order, from
+    the device tensor `src` into `pool`.  Returns the pages each entry pasted
+    (int32 device tensor, -1 = invalid entry); clone.pasted keeps the running
+    total.  No host sync."""
+    import numpy as np
+    torch = _torch()
+    rec = log_records(dst_off, src_off, lens)
+    n = rec.size
+    with _on_stream(stream):
+        per_entry = torch.zeros(max(n, 1), dtype=torch.int32, device=pool.device)
+        if n == 0:
+            return per_entry[:0]
+        d_pastes = torch.from_numpy(rec.view(np.uint8)).to(pool.device)
+    paste_records(pool, page_crcs, src, d_pastes, n, clone, per_entry, page_bytes=page_bytes, stream=stream)
+    if stream is not None:
+        for t in (d_pastes, per_entry):
+            t.record_stream(stream)
+    return per_entry[:n]
+
+
+def clone_mark(pool, d_log, n_updates: int, max_len: int, clone: Clone, page_bytes: int = PAGE_SIZE, stream=None):
+    """cc_clone_mark_dev: after apply_log* of the same log on the same stream,
+    set the bit of every page of a clone chunk that a valid entry covered whole
+    (flush() after Write).  A partly covered page keeps its bit."""
+    torch = _torch()
+    cs = clone.struct()
+    with torch.cuda.device(pool.device):
+        check(lib().cc_clone_mark_dev(_nbytes(pool), page_bytes, _dev_ptr(d_log, "log"), n_updates, max_len,
+                                      ctypes.byref(cs), _stream_handle(stream)), "cc_clone_mark_dev")
+    if stream is not None:
+        _record_clone(clone, stream)
+
+
+def clone_check_reads(pool, offsets, lengths, clone: Clone, page_bytes: int = PAGE_SIZE, stream=None):
+    """cc_clone_check_reads_dev: for the reads (offsets, lengths; any
+    alignment) of the pool, how many of the pages each touches lie in a clone
+    chunk and were never written.  Returns (unwritten_per_read int32 device
+    tensor, -1 = read past the pool; unwritten_total int64 [1]).  A read with
+    count 0 may be served (verify_reads / read_snap); any other needs its
+    origin fetched and pasted first.  No host sync."""
+    import numpy as np
+    torch = _torch()
+    off = np.asarray(offsets, dtype=np.uint64)
+    ln = np.asarray(lengths, dtype=np.uint64)
+    if off.size != ln.size:
+        raise CurveCrcError(_lib.CC_EINVAL, "offsets/lengths size mismatch")
+    n = off.size
+    with _on_stream(stream):
+        unwritten = torch.zeros(max(n, 1), dtype=torch.int32, device=pool.device)
+        total = torch.zeros(1, dtype=torch.int64, device=pool.device)
+        if n == 0:
+            return unwritten[:0], total
+        rng = torch.from_numpy(np.stack([off, ln], axis=1).reshape(-1).view(np.int64)).to(pool.device)
+    cs = clone.struct()
+    with torch.cuda.device(pool.device):
+        check(lib().cc_clone_check_reads_dev(_nbytes(pool), page_bytes, _dev_ptr(rng, "reads"), n, ctypes.byref(cs),
+                                             _dev_ptr(unwritten, "unwritten"), _dev_ptr(total, "total"),
+                                             _stream_handle(stream)), "cc_clone_check_reads_dev")
+    if stream is not None:
+        _record_clone(clone, stream)
+        for t in (rng, unwritten, total):
+            t.record_stream(stream)
+    return unwritten[:n], total
+
+
 def scan_files(paths, chunk_bytes: int = CHUNK_SIZE, meta_bytes: int = META_PAGE_SIZE,
                page_bytes: int = PAGE_SIZE, slice_bytes: int = SCAN_SIZE, io_threads: int = 0):
     """cc_scan_files: native pread + scan of chunk files.

@@ -1979,6 +1979,111 @@ int cc_read_snap_dev(const void* d_pool, uint64_t pool_bytes, uint32_t page_byte
                                       }));
 }
 
+namespace {
+// The checks the three clone calls share, and the kernels' view of a cc_clone.
+bool clone_ok(const cc_clone* cl, uint64_t pool_bytes, uint32_t page_bytes) {
+    if (!cl || !cl->d_clone_slot || !cl->d_bitmap || !cl->d_claim) return false;
+    return cl->chunk_bytes != 0 && cl->chunk_bytes % page_bytes == 0 && pool_bytes % cl->chunk_bytes == 0;
+}
+CloneGeo clone_geo(const cc_clone* cl, uint32_t page_bytes) {
+    CloneGeo g = {};
+    g.pages_per_chunk = cl->chunk_bytes / page_bytes;
+    g.words_per_slot = (g.pages_per_chunk + 31) / 32;
+    g.n_slots = cl->n_slots;
+    const uint64_t m = snap_recip(g.pages_per_chunk);
+    g.ppc_mlo = (uint32_t)m;
+    g.ppc_mhi = (uint32_t)(m >> 32);
+    g.clone_slot = cl->d_clone_slot;
+    g.bitmap = cl->d_bitmap;
+    g.claim = cl->d_claim;
+    return g;
+}
+}  // namespace
+
+int cc_paste_dev(void* d_pool, uint64_t pool_bytes, uint32_t page_bytes, const void* d_src, uint64_t src_bytes,
+                 const cc_update* d_pastes, uint64_t n, uint32_t* d_page_crcs, const cc_clone* clone,
+                 uint32_t* d_pasted_per_entry, void* stream) {
+    if (!log_page_ok(page_bytes)) return CC_EINVAL;
+    if (n == 0) return CC_OK;
+    if (n >= (1ull << 31)) return CC_EINVAL;  // entry indices live in d_claim, all-ones reserved
+    if (!d_pool || !d_src || !d_pastes || !d_page_crcs || !d_pasted_per_entry) return CC_EINVAL;
+    if (pool_bytes % page_bytes || ((uintptr_t)d_pool & 3u) || ((uintptr_t)d_src & 3u)) return CC_EINVAL;
+    if (!clone_ok(clone, pool_bytes, page_bytes)) return CC_EINVAL;
+    CtxRef c;
+    int rc = get_ctx(&c);
+    if (rc) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    PasteLaunch a = {};
+    a.pool = static_cast<uint32_t*>(d_pool);
+    a.pool_bytes = pool_bytes;
+    a.page_bytes = page_bytes;
+    a.page_shift = (uint32_t)__builtin_ctz(page_bytes);  // a power of two (log_page_ok)
+    a.src = static_cast<const unsigned char*>(d_src);
+    a.src_bytes = src_bytes;
+    a.pastes = reinterpret_cast<const UpdateDesc*>(d_pastes);
+    a.n = n;
+    a.page_crcs = d_page_crcs;
+    a.geo = clone_geo(clone, page_bytes);
+    a.pasted = reinterpret_cast<unsigned long long*>(clone->d_pasted);
+    a.pasted_per_entry = d_pasted_per_entry;
+    a.image = c->image;
+    a.kconst = kconst_for(page_bytes);
+    a.blocks = c->cus;
+    // the claim launch also marks the invalid entries; with no bitmaps nothing can be pasted
+    hipError_t e = launch_paste_claim(a, s);
+    if (e != hipSuccess || a.geo.n_slots == 0) return map_err(e);
+    return map_err(with_range_scratch(c.get(), s, 0,
+                                      [&](uint64_t* tiles, unsigned long long* tail, uint32_t*, uint32_t epoch) {
+                                          a.tiles = tiles;
+                                          a.tail = tail;
+                                          a.epoch = epoch;
+                                          return launch_paste(a, s);
+                                      }));
+}
+
+int cc_clone_mark_dev(uint64_t pool_bytes, uint32_t page_bytes, const cc_update* d_log, uint64_t n_updates,
+                      uint32_t max_len, const cc_clone* clone, void* stream) {
+    if (!log_page_ok(page_bytes)) return CC_EINVAL;
+    if (n_updates == 0) return CC_OK;
+    if (n_updates >= (1ull << 31) || !d_log || max_len == 0 || pool_bytes % page_bytes) return CC_EINVAL;
+    if (!clone_ok(clone, pool_bytes, page_bytes)) return CC_EINVAL;
+    CtxRef c;
+    int rc = get_ctx(&c);
+    if (rc) return rc;
+    CloneMarkLaunch a = {};
+    a.geo = clone_geo(clone, page_bytes);
+    a.pool_bytes = pool_bytes;
+    a.page_bytes = page_bytes;
+    a.page_shift = (uint32_t)__builtin_ctz(page_bytes);
+    a.max_len = max_len;
+    a.log = reinterpret_cast<const UpdateDesc*>(d_log);
+    a.n = n_updates;
+    a.blocks = c->cus;
+    return map_err(launch_clone_mark(a, static_cast<hipStream_t>(stream)));
+}
+
+int cc_clone_check_reads_dev(uint64_t pool_bytes, uint32_t page_bytes, const cc_range* d_reads, uint64_t n_reads,
+                             const cc_clone* clone, uint32_t* d_unwritten_per_read, uint64_t* d_unwritten_total,
+                             void* stream) {
+    if (!log_page_ok(page_bytes)) return CC_EINVAL;
+    if (n_reads == 0) return CC_OK;
+    if (n_reads >= (1ull << 31) || !d_reads || !d_unwritten_per_read || !d_unwritten_total) return CC_EINVAL;
+    if (pool_bytes % page_bytes || !clone_ok(clone, pool_bytes, page_bytes)) return CC_EINVAL;
+    CtxRef c;
+    int rc = get_ctx(&c);
+    if (rc) return rc;
+    CloneCheckLaunch a = {};
+    a.geo = clone_geo(clone, page_bytes);
+    a.pool_bytes = pool_bytes;
+    a.page_shift = (uint32_t)__builtin_ctz(page_bytes);
+    a.reads = reinterpret_cast<const RangeDesc*>(d_reads);
+    a.n = n_reads;
+    a.unwritten_per_read = d_unwritten_per_read;
+    a.unwritten_total = reinterpret_cast<unsigned long long*>(d_unwritten_total);
+    a.blocks = c->cus;
+    return map_err(launch_clone_check(a, static_cast<hipStream_t>(stream)));
+}
+
 // Streaming scan.  Each staging slot holds a batch of whole chunks (data and
 // metapages in separate device regions) plus the per-chunk results; a batch is
 // {H2D data+meta, page kernel over data, page kernel over metapages, fused

@@ -296,6 +296,71 @@ inline uint64_t snap_recip(uint32_t d) { return d > 1 ? ~0ull / d + 1 : 0; }
 hipError_t launch_snap_read(const SnapReadLaunch& a, hipStream_t s);
 // <= 64 reads in one launch (no tiles, no scratch)
 hipError_t launch_snap_read_small(const SnapReadLaunch& a, hipStream_t s);
+// Clone chunks (cc_paste_dev, cc_clone_mark_dev, cc_clone_check_reads_dev): the
+// written-page bitmaps of cc_clone.  Chunk c's bitmap is slot clone_slot[c]
+// (>= n_slots: not a clone chunk); page q of a slot is bit q % 32 of word q / 32.
+struct CloneGeo {
+    uint32_t pages_per_chunk;
+    uint32_t words_per_slot;     // bitmap words a slot: ceil(pages_per_chunk / 32)
+    uint32_t n_slots;
+    uint32_t ppc_mlo, ppc_mhi;   // snap_recip(pages_per_chunk)
+    const uint32_t* clone_slot;  // [chunks]
+    uint32_t* bitmap;            // n_slots x words_per_slot
+    uint32_t* claim;             // n_slots x pages_per_chunk, all 0xFFFFFFFF between calls (paste only)
+};
+// cc_paste_dev: an ORDERED batch of Paste requests in two launches.  The claim
+// launch leaves in claim[s * pages_per_chunk + q] the lowest index of the valid
+// entries covering a clone page whose bit is clear (and marks the invalid
+// entries); the paste launch walks the batch's (entry, page) slots on
+// verify-on-read's schedule, and the slot that finds its own index in the claim
+// word copies its source page into the pool, hashing it on the way, writes the
+// CRC, sets the bit, counts, and resets the claim word.
+struct PasteLaunch {
+    uint32_t* pool;
+    uint64_t pool_bytes;
+    uint32_t page_bytes;
+    uint32_t page_shift;         // log2(page_bytes)
+    const unsigned char* src;
+    uint64_t src_bytes;
+    const UpdateDesc* pastes;
+    uint64_t n;
+    uint32_t* page_crcs;
+    CloneGeo geo;
+    unsigned long long* pasted;  // += pages pasted, or null
+    uint32_t* pasted_per_entry;  // [n] += pages entry i pasted; UINT32_MAX for an invalid entry
+    uint64_t* tiles;             // the stream's range scratch, as ReadVerifyLaunch
+    unsigned long long* tail;
+    uint32_t epoch;
+    const void* image;
+    uint32_t kconst;
+    int blocks;                  // CUs
+};
+hipError_t launch_paste_claim(const PasteLaunch& a, hipStream_t s);
+hipError_t launch_paste(const PasteLaunch& a, hipStream_t s);
+// cc_clone_mark_dev: the bits of the pages a write log covered whole (one launch; reads no page)
+struct CloneMarkLaunch {
+    CloneGeo geo;
+    uint64_t pool_bytes;
+    uint32_t page_bytes;
+    uint32_t page_shift;
+    uint32_t max_len;
+    const UpdateDesc* log;
+    uint64_t n;
+    int blocks;                  // CUs
+};
+hipError_t launch_clone_mark(const CloneMarkLaunch& a, hipStream_t s);
+// cc_clone_check_reads_dev: per read, the touched pages of clone chunks whose bit is clear (one launch)
+struct CloneCheckLaunch {
+    CloneGeo geo;
+    uint64_t pool_bytes;
+    uint32_t page_shift;
+    const RangeDesc* reads;
+    uint64_t n;
+    uint32_t* unwritten_per_read;   // [n] += ; UINT32_MAX for a read past the pool
+    unsigned long long* unwritten_total;
+    int blocks;                  // CUs
+};
+hipError_t launch_clone_check(const CloneCheckLaunch& a, hipStream_t s);
 // CRC32C (butil Value) of arbitrary byte ranges of one device buffer, on the
 // flat block schedule, ONE launch: range_flat_kernel counts the
 // 4 KiB blocks of kRangeTiles contiguous tiles of the batch itself (epoch-tagged

@@ -2657,6 +2657,352 @@ __global__ __launch_bounds__(64 * kRvWaves) void snap_read_small_kernel(SnapRead
     }
 }
 
+// ---------------------------------------------------------------------------
+// Clone chunks (cc_paste_dev, cc_clone_mark_dev, cc_clone_check_reads_dev):
+// the written-page bitmap of a lazily allocated chunk on the device.  Replaces
+// the host loops of CSChunkFile::Paste (chunkserver_chunkfile.cpp:440-495:
+// Divide(begin, end, &uncopied, nullptr), writeData per uncopied range, then
+// flush() sets the bits), of flush() after a Write (:405-406, :965-1000) and of
+// Read's NextClearBit test (:510-526).
+// ---------------------------------------------------------------------------
+// page / pages_per_chunk: the host-made reciprocal below 2^32 pages (snap_recip), a division beyond
+__device__ __forceinline__ uint64_t clone_chunk_of(const CloneGeo& g, uint64_t page) {
+    if ((page >> 32) || g.pages_per_chunk == 1) return page / g.pages_per_chunk;
+    const uint32_t p32 = (uint32_t)page;
+    return ((uint64_t)p32 * g.ppc_mhi + ((uint64_t)p32 * g.ppc_mlo >> 32)) >> 32;
+}
+
+// The three one-launch passes walk (entry, page) pairs with one LANE per pair
+// and no page traffic: a wave takes 64 entries at a time (lane j <- entry
+// base + j: load(i, first page, pages); 0 pages for an entry that takes no
+// part), lays their pages out as one stream with a wave prefix sum and walks
+// the stream 64 pairs a step; a lane finds its pair's entry with a binary
+// search over the prefix sums (six shuffles) and calls fn(entry, pool page).
+constexpr int kCloneWaves = 4;  // waves per workgroup of the claim, mark and check kernels
+template <typename Load, typename Fn>
+__device__ __forceinline__ void clone_entry_pages(uint64_t n, uint32_t lane, Load load, Fn fn) {
+    const uint64_t Wg = (uint64_t)gridDim.x * kCloneWaves;
+    const uint64_t w = (uint64_t)blockIdx.x * kCloneWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    for (uint64_t base = w * 64; base < n; base += Wg * 64) {
+        uint64_t p0 = 0, cnt = 0;
+        if (base + lane < n) load(base + lane, p0, cnt);
+        const uint64_t cum = wave_scan_incl(cnt, lane);
+        const uint64_t P = readlane64(cum, 63);
+        for (uint64_t k0 = 0; k0 < P; k0 += 64) {
+            const bool on = k0 + lane < P;
+            const uint64_t k = on ? k0 + lane : P - 1;
+            uint32_t o = 0;  // entries of the group whose pages end at or before pair k: the pair's entry
+#pragma unroll
+            for (int d = 32; d; d >>= 1)
+                if (__shfl(cum, (int)(o + d - 1), 64) <= k) o += d;
+            const uint64_t upto = __shfl(cum, (int)(o ? o - 1 : 0), 64);
+            const uint64_t first = __shfl(p0, (int)o, 64);
+            if (on) fn(base + o, first + (k - (o ? upto : 0)));
+        }
+    }
+}
+
+// An entry that cc_paste_dev skips whole: misaligned dst or len, past the
+// pool, a source range that is unaligned or leaves the buffer (len == 0 is
+// valid and covers nothing).
+__device__ __forceinline__ bool paste_bad(const PasteLaunch& a, const UpdateDesc& u) {
+    if (!u.len) return false;
+    if ((u.dst | u.len) & (uint64_t)(a.page_bytes - 1u)) return true;
+    if (u.dst >= a.pool_bytes || u.len > a.pool_bytes - u.dst) return true;
+    return (u.src & 3u) || u.src > a.src_bytes || u.len > a.src_bytes - u.src;
+}
+__device__ __forceinline__ uint32_t paste_pages(const PasteLaunch& a, const UpdateDesc& u) {
+    return paste_bad(a, u) ? 0u : u.len >> a.page_shift;
+}
+
+// Launch 1 of cc_paste_dev: every (valid entry, page) pair whose chunk is a
+// clone and whose bit is clear bids for the page with its entry index; the
+// lowest index holds the claim word when the launch ends.  The lane that loads
+// an invalid entry marks it.  Reads the bitmap; the paste launch sets bits only
+// after this one has finished.
+__global__ __launch_bounds__(64 * kCloneWaves) void paste_claim_kernel(PasteLaunch a) {
+    const uint32_t lane = threadIdx.x & 63u;
+    clone_entry_pages(
+        a.n, lane,
+        [&](uint64_t i, uint64_t& p0, uint64_t& cnt) {
+            const UpdateDesc u = a.pastes[i];
+            if (paste_bad(a, u)) {
+                a.pasted_per_entry[i] = 0xFFFFFFFFu;
+                return;
+            }
+            p0 = u.dst >> a.page_shift;
+            cnt = u.len >> a.page_shift;
+        },
+        [&](uint64_t e, uint64_t page) {
+            const uint64_t c = clone_chunk_of(a.geo, page);
+            const uint32_t q = (uint32_t)(page - c * a.geo.pages_per_chunk);
+            const uint32_t s = a.geo.clone_slot[c];
+            if (s >= a.geo.n_slots) return;  // not a clone chunk
+            const uint32_t word = a.geo.bitmap[(uint64_t)s * a.geo.words_per_slot + (q >> 5)];
+            if ((word >> (q & 31u)) & 1u) return;  // written already: the page keeps its bytes
+            atomicMin(a.geo.claim + (uint64_t)s * a.geo.pages_per_chunk + q, (uint32_t)e);
+        });
+}
+
+// Pages of tile t of the paste batch, uniform (snap_tile_count without the marks: the claim launch made them).
+__device__ __forceinline__ uint64_t paste_tile_count(const PasteLaunch& a, uint32_t t, uint32_t lane) {
+    const uint64_t lo = a.n * t / kReadTiles, hi = a.n * (t + 1) / kReadTiles;
+    uint64_t sum = 0;
+    for (uint64_t i = lo + lane; i < hi; i += 64) sum += paste_pages(a, a.pastes[i]);
+#pragma unroll
+    for (int d = 32; d; d >>= 1) sum += __shfl_xor(sum, d, 64);
+    return sum;
+}
+
+// One (entry, page) slot of the paste launch on its way to its loads, resolved
+// in stages a step apart as snap_read_kernel resolves its pages: paste_slot_of
+// (chunk, page in chunk, the chunk's bitmap slot), paste_claim_of (the page's
+// claim word), and the comparison with the slot's own entry index.  Both table
+// words come in with vector loads of a uniform address and stay in a VGPR until
+// the next stage takes them a step later.
+struct PastePg {
+    uint64_t g;      // pool page
+    uint32_t owner;  // lane holding the page's entry
+    uint32_t rel;    // the page's position in its entry
+    uint32_t q;      // page in chunk
+    uint32_t s;      // the chunk's bitmap slot (>= n_slots: not a clone), once paste_claim_of has taken it
+    uint32_t sv;     // VGPR: the slot as loaded
+    uint32_t cv;     // VGPR: the page's claim word as loaded
+};
+__device__ __forceinline__ void paste_slot_of(const PasteLaunch& a, PastePg& p, uint32_t vz) {
+    const uint64_t c = clone_chunk_of(a.geo, p.g);
+    p.q = (uint32_t)(p.g - c * a.geo.pages_per_chunk);
+    p.s = 0xFFFFFFFFu;
+    p.cv = 0xFFFFFFFFu;
+    p.sv = a.geo.clone_slot[c + vz];
+}
+__device__ __forceinline__ void paste_claim_of(const PasteLaunch& a, PastePg& p, uint32_t vz) {
+    p.s = __builtin_amdgcn_readfirstlane(p.sv);
+    const uint32_t sc = p.s < a.geo.n_slots ? p.s : 0u;  // clamped: the same load every slot (n_slots >= 1 here)
+    p.cv = a.geo.claim[(uint64_t)sc * a.geo.pages_per_chunk + p.q + vz];
+}
+// A slot whose loads are out: where its page goes when it holds the claim.
+struct PasteDst {
+    uint64_t g;
+    uint32_t owner, s, q;
+    bool win;
+};
+
+// Launch 2 of cc_paste_dev, on read_verify_kernel's schedule (tile counts
+// published by the waves, shares at slot granularity, 1/16 dynamic tail, three
+// register sets rotating) over the batch's (entry, page) slots.  The slot whose
+// claim word equals its own entry index is the page's winner: its source page is
+// loaded two steps ahead, hashed as it passes through the registers, stored to
+// the pool, and the lane-0 epilogue writes the CRC, ORs the bit, counts and puts
+// 0xFFFFFFFF back into the claim word.  Every other slot issues no page load
+// and hashes nothing.  A loser may read the claim word before or after the
+// winner's reset: neither value is its own index (only entry i ever writes i,
+// and only the slot that found i there resets it), so no third launch is needed.
+template <int M>
+__global__ __launch_bounds__(64 * kRvWaves) void paste_kernel(PasteLaunch a) {
+    __shared__ uint32_t tab[kLdsBytes / 4];
+    const uint64_t n = a.n;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint64_t Wg = (uint64_t)gridDim.x * kRvWaves;
+    const uint64_t w = (uint64_t)blockIdx.x * kRvWaves + wave;
+    const uint64_t tag = (uint64_t)a.epoch << kEpochShift;
+    for (uint64_t t = w; t < kReadTiles; t += Wg) {
+        const uint64_t cnt = paste_tile_count(a, (uint32_t)t, lane);
+        if (lane == 0) __hip_atomic_store(a.tiles + t, tag | cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    unsigned long long* dyn_ctr = a.tail + (a.epoch & 1u) * kDynCtrWords64;
+    if (blockIdx.x == 0 && threadIdx.x < kRvHeads)
+        atomicExch(a.tail + ((a.epoch + 1u) & 1u) * kDynCtrWords64 + threadIdx.x * kDynHeadStride, 0ull);
+    fill_lds<64 * kRvWaves>(tab, static_cast<const uint4*>(a.image));
+    const uint32_t c0 = lane << 2 & 0x7Cu;
+    const uint32_t c1 = c0 | 0x10000u;
+    const uint32_t cf = kFinBase + (lane << 2);
+    uint32_t vz = 0;
+    asm volatile("" : "+v"(vz));  // opaque zero: keeps uniform-address loads on the vector path
+
+    constexpr int kTpl = kReadTiles / 64;
+    uint64_t tb[kTpl];
+    wait_tiles<kTpl>(tb, a.tiles, tag, lane, [&](uint32_t t) { return paste_tile_count(a, t, lane); });
+    uint64_t lsum = 0;
+#pragma unroll
+    for (int j = 0; j < kTpl; j++) lsum += tb[j];
+    const uint64_t cum = wave_scan_incl(lsum, lane);
+    const uint64_t T = readlane64(cum, 63);
+    const uint64_t Wt = (T + kRvMinSlots - 1) / kRvMinSlots;
+    const uint64_t W = Wt < Wg ? (Wt ? Wt : 1) : Wg;
+    if ((uint64_t)blockIdx.x * kRvWaves >= W) return;  // uniform per block: no share, no tail
+    const uint64_t Ts = T - T / kRvDynDiv;
+    uint32_t dyn_head, dyn_tried;
+    tail_cursor<kRvHeads>(dyn_head, dyn_tried);
+    uint64_t lo_slot = w < W ? Ts * w / W : Ts, hi_slot = w < W ? Ts * (w + 1) / W : Ts;  // waves past W: tail only
+    uint32_t npasted = 0;  // uniform: this wave's pasted pages, added to the total once
+#pragma unroll 1
+    for (;;) {
+        uint64_t base = n, S = 0;
+        UpdateDesc us;
+        bool have_us = false;
+        if (lo_slot < hi_slot) {
+            const TileHit th = tile_of(cum, tb, lo_slot, lane);
+            base = n * th.tile / kReadTiles;
+            S = th.before;
+            for (;;) {
+                const uint64_t ei = base + lane;
+                us = a.pastes[(ei < n ? ei : base) + vz];
+                const uint64_t c = wave_scan_incl(ei < n ? paste_pages(a, us) : 0u, lane);
+                const uint64_t tot = readlane64(c, 63);
+                if (S + tot > lo_slot || base + 64 >= n) break;
+                S += tot;
+                base += 64;
+            }
+            have_us = true;
+        }
+        for (; base < n && S < hi_slot; base += 64) {
+            const uint64_t ei = base + lane;
+            const bool valid = ei < n;
+            const UpdateDesc u = have_us ? us : a.pastes[(valid ? ei : base) + vz];
+            have_us = false;
+            const uint32_t cnt = valid ? paste_pages(a, u) : 0u;  // 0 also for invalid entries
+            const uint64_t p0 = u.dst >> a.page_shift;
+            const uint64_t so = u.src;
+            uint32_t cum32 = cnt;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const uint32_t o = __shfl_up(cum32, d, 64);
+                if (lane >= (uint32_t)d) cum32 += o;
+            }
+            const uint32_t P = __builtin_amdgcn_readlane(cum32, 63);
+            const uint32_t ks = lo_slot > S ? (uint32_t)(lo_slot - S) : 0u;
+            const uint32_t ke = hi_slot - S < (uint64_t)P ? (uint32_t)(hi_slot - S) : P;
+            S += P;
+            if (ks >= ke) continue;
+            // slot k (clamped to the share's last): its entry's lane, its page, its chunk's bitmap slot
+            auto locate = [&](uint32_t k) {
+                k = k < ke ? k : ke - 1;
+                PastePg p;
+                p.owner = (uint32_t)__builtin_ctzll(__ballot(cum32 > k));
+                const uint32_t before = p.owner ? (uint32_t)__builtin_amdgcn_readlane(cum32, p.owner - 1) : 0u;
+                p.rel = k - before;
+                p.g = readlane64(p0, p.owner) + p.rel;
+                paste_slot_of(a, p, vz);
+                return p;
+            };
+            // the resolved slot: does it hold its page's claim?  Then the slot
+            // behind it moves up (its claim word, and the bitmap slot of the one
+            // after), and the winner's source page is loaded
+            PastePg p3, p4;
+            auto issue = [&](uint32_t kn, uint32_t (&Y)[M], PasteDst& dy) {
+                const uint32_t holder = __builtin_amdgcn_readfirstlane(p3.cv);
+                dy.g = p3.g;
+                dy.owner = p3.owner;
+                dy.s = p3.s;
+                dy.q = p3.q;
+                dy.win = p3.s < a.geo.n_slots && holder == (uint32_t)base + p3.owner;
+                const uint64_t from = readlane64(so, p3.owner) + ((uint64_t)p3.rel << a.page_shift);
+                p3 = p4;
+                paste_claim_of(a, p3, vz);
+                p4 = locate(kn);
+                __builtin_amdgcn_sched_barrier(0);  // the table loads stay ahead of the page's
+                if (dy.win) load_page<M>(Y, reinterpret_cast<const uint32_t*>(a.src + from) + lane);
+            };
+            uint32_t A[M], B[M], Cq[M];
+            PasteDst dA, dB, dC;
+            p3 = locate(ks);
+            paste_claim_of(a, p3, vz);
+            p4 = locate(ks + 1);
+            issue(ks + 2, A, dA);
+            issue(ks + 3, B, dB);
+            dC = dB;
+            // slot k (registers X when it won); slot k+2's loads go into Y
+            auto step = [&](uint32_t (&X)[M], const PasteDst dx, uint32_t k, uint32_t (&Y)[M], PasteDst& dy) {
+                const bool more = k + 1 < ke;
+                issue(k + 4, Y, dy);
+                if (dx.win) {
+                    const uint32_t crc = wave_xor(apply_fin(tab, chain<M>(tab, X, c0, c1), cf)) ^ a.kconst;
+                    store_page<M>(X, a.pool + (dx.g << (a.page_shift - 2u)) + lane);
+                    if (lane == 0) {
+                        a.page_crcs[dx.g] = crc;
+                        atomicOr(a.geo.bitmap + (uint64_t)dx.s * a.geo.words_per_slot + (dx.q >> 5), 1u << (dx.q & 31u));
+                        atomicAdd(a.pasted_per_entry + base + dx.owner, 1u);
+                        __hip_atomic_store(a.geo.claim + (uint64_t)dx.s * a.geo.pages_per_chunk + dx.q, 0xFFFFFFFFu,
+                                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    }
+                    npasted++;
+                }
+                return more;
+            };
+            for (uint32_t k = ks;; k += 3) {
+                if (!step(A, dA, k, Cq, dC)) break;
+                if (!step(B, dB, k + 1, A, dA)) break;
+                if (!step(Cq, dC, k + 2, B, dB)) break;
+            }
+        }
+        const uint64_t n_dyn = (T - Ts + kRvDynSlots - 1) / kRvDynSlots;
+        const uint64_t c = tail_pull<kRvHeads>(dyn_ctr, n_dyn, dyn_head, dyn_tried, lane);
+        if (c >= n_dyn) break;
+        lo_slot = Ts + c * kRvDynSlots;
+        hi_slot = lo_slot + kRvDynSlots < T ? lo_slot + kRvDynSlots : T;
+    }
+    if (npasted && lane == 0 && a.pasted) atomicAdd(a.pasted, (unsigned long long)npasted);
+}
+
+// cc_clone_mark_dev: flush()'s bitmap step after a write log.  Every page that
+// a valid entry (the write log's contract) covers WHOLE and whose chunk is a
+// clone gets its bit set; a partly covered page keeps its bit.
+__global__ __launch_bounds__(64 * kCloneWaves) void clone_mark_kernel(CloneMarkLaunch a) {
+    const uint32_t lane = threadIdx.x & 63u;
+    clone_entry_pages(
+        a.n, lane,
+        [&](uint64_t i, uint64_t& p0, uint64_t& cnt) {
+            const UpdateDesc u = a.log[i];
+            if (!u.len || u.len > a.max_len || u.dst >= a.pool_bytes || u.len > a.pool_bytes - u.dst) return;
+            const uint64_t first = (u.dst >> a.page_shift) + ((u.dst & (uint64_t)(a.page_bytes - 1u)) ? 1u : 0u);
+            const uint64_t end = (u.dst + u.len) >> a.page_shift;
+            p0 = first;
+            cnt = end > first ? end - first : 0u;
+        },
+        [&](uint64_t, uint64_t page) {
+            const uint64_t c = clone_chunk_of(a.geo, page);
+            const uint32_t q = (uint32_t)(page - c * a.geo.pages_per_chunk);
+            const uint32_t s = a.geo.clone_slot[c];
+            if (s >= a.geo.n_slots) return;
+            atomicOr(a.geo.bitmap + (uint64_t)s * a.geo.words_per_slot + (q >> 5), 1u << (q & 31u));
+        });
+}
+
+// cc_clone_check_reads_dev: Read's NextClearBit test for a batch.  Every page a
+// read touches that lies in a clone chunk with a clear bit counts on its read;
+// a read past the pool is marked by the lane that loads it.
+__global__ __launch_bounds__(64 * kCloneWaves) void clone_check_kernel(CloneCheckLaunch a) {
+    const uint32_t lane = threadIdx.x & 63u;
+    uint64_t mine = 0;  // this lane's hits, summed over the wave for the total
+    clone_entry_pages(
+        a.n, lane,
+        [&](uint64_t i, uint64_t& p0, uint64_t& cnt) {
+            const RangeDesc r = a.reads[i];
+            if (!r.len) return;
+            if (r.off >= a.pool_bytes || r.len > a.pool_bytes - r.off) {
+                a.unwritten_per_read[i] = 0xFFFFFFFFu;
+                return;
+            }
+            p0 = r.off >> a.page_shift;
+            cnt = ((r.off + r.len - 1) >> a.page_shift) - p0 + 1;
+        },
+        [&](uint64_t e, uint64_t page) {
+            const uint64_t c = clone_chunk_of(a.geo, page);
+            const uint32_t q = (uint32_t)(page - c * a.geo.pages_per_chunk);
+            const uint32_t s = a.geo.clone_slot[c];
+            if (s >= a.geo.n_slots) return;
+            const uint32_t word = a.geo.bitmap[(uint64_t)s * a.geo.words_per_slot + (q >> 5)];
+            if ((word >> (q & 31u)) & 1u) return;
+            atomicAdd(a.unwritten_per_read + e, 1u);
+            mine++;
+        });
+#pragma unroll
+    for (int d = 32; d; d >>= 1) mine += __shfl_xor(mine, d, 64);
+    if (mine && lane == 0) atomicAdd(a.unwritten_total, (unsigned long long)mine);
+}
+
 __global__ void combine_kernel(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b, uint32_t m,
                                uint64_t n, uint32_t* __restrict__ out) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -2978,6 +3324,49 @@ hipError_t launch_snap_read(const SnapReadLaunch& a, hipStream_t s) {
         default: return hipErrorInvalidValue;
     }
 #undef CC_RCASE
+    return hipGetLastError();
+}
+
+// a wave per 64 entries, up to 8 workgroups a CU
+static dim3 clone_grid(uint64_t n, int cus) {
+    const uint64_t want = (n + 64ull * kCloneWaves - 1) / (64ull * kCloneWaves), cap = 8ull * (uint64_t)(cus > 0 ? cus : 1);
+    return dim3((unsigned)(want < cap ? (want ? want : 1) : cap));
+}
+
+hipError_t launch_paste_claim(const PasteLaunch& a, hipStream_t s) {
+    if (a.n == 0) return hipSuccess;
+    hipLaunchKernelGGL(paste_claim_kernel, clone_grid(a.n, a.blocks), dim3(64 * kCloneWaves), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_paste(const PasteLaunch& a, hipStream_t s) {
+    if (a.n == 0 || a.geo.n_slots == 0) return hipSuccess;
+#define CC_PCASE(MM)                                                                              \
+    case MM:                                                                                      \
+        hipLaunchKernelGGL((paste_kernel<MM>), dim3(a.blocks), dim3(64 * kRvWaves), 0, s, a);     \
+        break;
+    switch (a.page_bytes / kWaveBytes) {
+        CC_PCASE(1)
+        CC_PCASE(2)
+        CC_PCASE(4)
+        CC_PCASE(8)
+        CC_PCASE(16)
+        CC_PCASE(32)
+        default: return hipErrorInvalidValue;
+    }
+#undef CC_PCASE
+    return hipGetLastError();
+}
+
+hipError_t launch_clone_mark(const CloneMarkLaunch& a, hipStream_t s) {
+    if (a.n == 0 || a.geo.n_slots == 0) return hipSuccess;
+    hipLaunchKernelGGL(clone_mark_kernel, clone_grid(a.n, a.blocks), dim3(64 * kCloneWaves), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_clone_check(const CloneCheckLaunch& a, hipStream_t s) {
+    if (a.n == 0) return hipSuccess;
+    hipLaunchKernelGGL(clone_check_kernel, clone_grid(a.n, a.blocks), dim3(64 * kCloneWaves), 0, s, a);
     return hipGetLastError();
 }
 

@@ -450,6 +450,123 @@ int cc_read_snap_dev(const void* d_pool, uint64_t pool_bytes, uint32_t page_byte
                      const uint64_t* d_out_off, uint64_t out_bytes, uint32_t* d_bad_per_read, uint64_t* d_bad_total,
                      void* stream);
 
+/* Clone chunks: the written-page bitmap on the device.  A clone chunk is
+ * allocated lazily (clone, or recover from a snapshot in S3 or another volume)
+ * and carries, in its metapage, one bit per page that has been written; the
+ * three calls below are the three places where CSChunkFile looks at or changes
+ * that bitmap, for a pool some of whose chunks are clones.  A clone chunk can
+ * never open a snapshot (Write returns StatusConflictError,
+ * chunkserver_chunkfile.cpp:329-336), so these calls and cc_apply_log_cow_dev
+ * never meet on one chunk.
+ *
+ * The struct is a HOST struct of device pointers, like cc_cow, and follows its
+ * slot and bitmap conventions: chunk c's bitmap is slot d_clone_slot[c]; any
+ * value >= n_slots (CC_NOT_CLONE) says the chunk is not a clone, and nothing of
+ * it is ever looked up behind d_bitmap or d_claim.  d_claim is cc_paste_dev's
+ * scratch, kept by the caller beside the bitmaps: all 0xFFFFFFFF before the
+ * first call, and every call that completes leaves it so. */
+#define CC_NOT_CLONE 0xFFFFFFFFu
+typedef struct cc_clone {
+    uint32_t chunk_bytes;            /* a multiple of page_bytes that divides pool_bytes */
+    uint32_t n_slots;                /* clone bitmaps behind d_bitmap */
+    const uint32_t* d_clone_slot;    /* [pool_bytes / chunk_bytes]: chunk c's bitmap index; any value >= n_slots
+                                        (CC_NOT_CLONE) = not a clone chunk */
+    uint32_t* d_bitmap;              /* n_slots x ceil(pages_per_chunk / 32) words; bit q % 32 of word q / 32 =
+                                        bit q % 8 of byte q / 8: a slot's bytes ARE ChunkFileMetaPage's bitmap */
+    uint32_t* d_claim;               /* n_slots x pages_per_chunk words, all 0xFFFFFFFF on entry; every call that
+                                        completes leaves them so (the engine tables' convention) */
+    uint64_t* d_pasted;              /* optional: += pages pasted by cc_paste_dev */
+} cc_clone;
+
+/* Paste: origin data lands only where nothing was written yet.  Replaces the
+ * host loop of CSChunkFile::Paste (chunkserver_chunkfile.cpp:440-495:
+ * Divide(begin, end, &uncopied, nullptr), writeData per uncopied range, then
+ * flush() sets the bits; Success and nothing written on a non-clone chunk),
+ * which PasteChunkInternalRequest::OnApply runs for CloneCore::PasteCloneData
+ * (op_request.cpp:725-747, clone_core.cpp:418-460).  d_pastes[0..n) is an
+ * ORDERED batch, applied as n Paste calls in that order would be: concurrent
+ * reads of one unwritten region each fetch the origin and each paste, and the
+ * first paste applied wins every page.
+ *
+ * Per pool page, by its chunk and bit as they stood BEFORE the call: a page of
+ * a clone chunk whose bit is clear is written exactly once, from the
+ * LOWEST-indexed valid entry covering it -- its bytes are d_src + src_i +
+ * (page start - dst_i), its bit is set (an atomic OR on its word) and
+ * d_page_crcs[p] becomes the CRC of the new bytes, hashed as the page passes
+ * through registers; a page whose bit is set, and any page of a chunk that is
+ * not a clone, keeps its bytes and its CRC.  An entry may cross chunk
+ * boundaries: every page is resolved on its own, as in cc_read_snap_dev.
+ * d_pasted_per_entry[i] += the pages entry i pasted (the caller zeroes it),
+ * *clone->d_pasted += all of them.  With the lowest-index rule the pool, the
+ * CRC table, the bitmaps and both counts are deterministic.
+ *
+ * An entry is INVALID -- d_pasted_per_entry[i] = UINT32_MAX, nothing written,
+ * nothing claimed -- when dst or len is not a multiple of page_bytes
+ * (CheckOffsetAndLength, chunkserver_chunkfile.h:386-394), when it runs past
+ * the pool (dst >= pool_bytes or len > pool_bytes - dst), when src is not
+ * 4-byte aligned or when src + len > src_bytes.  len == 0 is valid: it touches
+ * nothing and leaves its word alone.  d_src must not alias d_pool.
+ *
+ * Checked before a device is needed (CC_EINVAL): page_bytes = 256 * 2^k
+ * (k = 0..5); pool_bytes whole pages; d_pool and d_src 4-byte aligned; d_pool,
+ * d_src, d_pastes, d_page_crcs, d_pasted_per_entry, clone and clone's
+ * d_clone_slot, d_bitmap, d_claim non-NULL; chunk_bytes a multiple of
+ * page_bytes that divides pool_bytes; n < 2^31 (entry indices live in d_claim,
+ * all-ones reserved).  n == 0 is CC_OK.  No GPU: CC_ENODEV, never a CPU
+ * fallback.
+ *
+ * Two launches on `stream`.  CLAIM: one lane per (valid entry, page), no page
+ * traffic; where the page's chunk is a clone and its bit is clear,
+ * atomicMin(d_claim[s * pages_per_chunk + q], i); it also marks the invalid
+ * entries.  PASTE: every (entry, page) pair is one slot on verify-on-read's
+ * schedule (the slots split evenly over the device, the last 1/16 dynamically,
+ * using the stream's range scratch the engine keeps: no caller work buffer);
+ * the slot whose claim word equals its entry index copies and hashes the page,
+ * writes the CRC, sets the bit, counts and puts 0xFFFFFFFF back; every other
+ * slot loads no page.  The bitmap is only read in the first launch and only
+ * written in the second.  The caller must not run another call over the same
+ * bitmaps on another stream at the same time. */
+int cc_paste_dev(void* d_pool, uint64_t pool_bytes, uint32_t page_bytes, const void* d_src, uint64_t src_bytes,
+                 const cc_update* d_pastes, uint64_t n, uint32_t* d_page_crcs, const cc_clone* clone,
+                 uint32_t* d_pasted_per_entry, void* stream);
+
+/* The flush() half of CSChunkFile::Write on clone chunks
+ * (chunkserver_chunkfile.cpp:405-406, :965-1000: the bits of the pages the
+ * write covered are set, so that a later Paste does not bury a user write
+ * under origin data).  Enqueue it after the cc_apply_log*_dev call for the
+ * same log on the same stream.  For every entry that keeps the write log's
+ * contract (1 <= len <= max_len, dst + len <= pool_bytes; any other entry is
+ * skipped, as the log call skips it), every page the entry covers WHOLE whose
+ * chunk is a clone gets its bit set.  A partly covered page keeps its bit --
+ * the reference only accepts block-aligned writes, and declaring a page
+ * written while part of it was never filled would let a read return garbage
+ * silently -- and two partial entries that together cover a page do not count.
+ * One launch; it touches neither d_claim nor any page.  The checks are
+ * cc_paste_dev's where they apply: page_bytes, pool_bytes whole pages, d_log
+ * and clone (with its three pointers) non-NULL, chunk_bytes, max_len >= 1,
+ * n_updates < 2^31; n_updates == 0 is CC_OK; no GPU: CC_ENODEV.  When the last
+ * bit of a chunk is set the chunk has become an ordinary one (:972-996): the
+ * caller sees that in the bitmap it reads back for the metapage. */
+int cc_clone_mark_dev(uint64_t pool_bytes, uint32_t page_bytes, const cc_update* d_log, uint64_t n_updates,
+                      uint32_t max_len, const cc_clone* clone, void* stream);
+
+/* The NextClearBit test of CSChunkFile::Read on a clone chunk
+ * (chunkserver_chunkfile.cpp:510-526: a range with any clear bit is refused
+ * with PageNerverWrittenError) and of CloneCore::HandleReadRequest
+ * (clone_core.cpp:166: must the origin be fetched at all), for a batch.  Reads
+ * are pool byte ranges of any offset and length, as for cc_verify_reads_dev; a
+ * partly covered page counts.  d_unwritten_per_read[i] += the pages of read i
+ * that lie in a clone chunk with a clear bit (the caller zeroes it),
+ * *d_unwritten_total += their sum; UINT32_MAX marks a read that runs past the
+ * pool; len == 0 touches nothing.  A non-zero count is the reference's
+ * PageNerverWrittenError, or "fetch the origin and cc_paste_dev it"; a read
+ * with count 0 may go to cc_verify_reads_dev or cc_read_snap_dev.  It reads
+ * bitmap words only, in one launch.  Checks as cc_paste_dev's where they
+ * apply, with d_reads and both counters non-NULL and n_reads < 2^31. */
+int cc_clone_check_reads_dev(uint64_t pool_bytes, uint32_t page_bytes, const cc_range* d_reads, uint64_t n_reads,
+                             const cc_clone* clone, uint32_t* d_unwritten_per_read, uint64_t* d_unwritten_total,
+                             void* stream);
+
 /* One chunk file as the datastore holds it: metapage + data
  * (file = metapage || data, chunkserver_chunkfile.cpp:497-536). */
 typedef struct cc_chunk_src {
