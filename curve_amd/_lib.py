@@ -104,6 +104,7 @@ class CcClone(ctypes.Structure):
 
 
 CC_NOT_CLONE = 0xFFFFFFFF
+CC_NO_ORIGIN = 0xFFFFFFFFFFFFFFFF  # cc_read_merge_dev: d_origin_off[i] of a read with no origin
 
 SIGNATURES = {
     "crc32c_value": (_u32, [_vp, _sz]),
@@ -162,6 +163,8 @@ SIGNATURES = {
     "cc_paste_dev": (_int, [_vp, _u64, _u32, _vp, _u64, _vp, _u64, _vp, ctypes.POINTER(CcClone), _vp, _vp]),
     "cc_clone_mark_dev": (_int, [_u64, _u32, _vp, _u64, _u32, ctypes.POINTER(CcClone), _vp]),
     "cc_clone_check_reads_dev": (_int, [_u64, _u32, _vp, _u64, ctypes.POINTER(CcClone), _vp, _vp, _vp]),
+    "cc_read_merge_dev": (_int, [_vp, _u64, _u32, _vp, _u64, _vp, ctypes.POINTER(CcClone), _vp, _vp, _u64, _vp, _vp,
+                                 _u64, _vp, _vp, _vp, _vp, _vp]),
     "cc_comm_unique_id": (_int, [_vp, _sz]),
     "cc_comm_init": (_int, [ctypes.POINTER(_vp), _int, _int, _vp, _sz]),
     "cc_comm_init_timeout": (_int, [ctypes.POINTER(_vp), _int, _int, _vp, _sz, _u32]),

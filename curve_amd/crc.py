@@ -970,6 +970,136 @@ def clone_check_reads(pool, offsets, lengths, clone: Clone, page_bytes: int = PA
     return unwritten[:n], total
 
 
+NO_ORIGIN = _lib.CC_NO_ORIGIN  # origin_off of a read that has no origin buffer
+
+
+def read_merge_records(pool, page_crcs, d_reads, n_reads: int, clone: Clone, out, out_off, bad, total, unwritten,
+                       unwritten_total, origin=None, origin_off=None, page_bytes: int = PAGE_SIZE, stream=None):
+    """cc_read_merge_dev on a batch already resident on the device: `d_reads` =
+    int64 device tensor of n_reads page-aligned (offset, length) pairs.  A
+    written page (no clone chunk, or its bit in `clone` set) is rehashed against
+    `page_crcs` and stored at out[out_off[i] + its position in read i]; a
+    never-written page comes from origin[origin_off[i] + the same position],
+    unhashed, or -- with origin=None or origin_off[i] = NO_ORIGIN -- leaves its
+    output bytes alone.  Mismatches are ADDED to `bad` / `total`, never-written
+    pages to `unwritten` / `unwritten_total` (int32 [n_reads] and int64 [1]
+    each; -1 in both per-read words marks an invalid read).  `out` uint8,
+    `out_off` / `origin_off` int64 [n_reads] device tensors.  Reads the bitmaps
+    only.  No host sync."""
+    torch = _torch()
+    if origin is not None and origin_off is None:
+        raise CurveCrcError(_lib.CC_EINVAL, "origin needs origin_off")
+    cs = clone.struct()
+    with torch.cuda.device(pool.device):
+        check(lib().cc_read_merge_dev(_dev_ptr(pool, "pool"), _nbytes(pool), page_bytes, _dev_ptr(d_reads, "reads"),
+                                      n_reads, _dev_ptr(page_crcs, "page_crcs"), ctypes.byref(cs),
+                                      _dev_ptr(origin, "origin") if origin is not None else None,
+                                      _dev_ptr(origin_off, "origin_off") if origin is not None else None,
+                                      _nbytes(origin) if origin is not None else 0, _dev_ptr(out, "out"),
+                                      _dev_ptr(out_off, "out_off"), _nbytes(out), _dev_ptr(bad, "bad"),
+                                      _dev_ptr(total, "total"), _dev_ptr(unwritten, "unwritten"),
+                                      _dev_ptr(unwritten_total, "unwritten_total"), _stream_handle(stream)),
+              "cc_read_merge_dev")
+    if stream is not None:
+        _record_clone(clone, stream)
+
+
+def read_merge(pool, page_crcs, offsets, lengths, clone: Clone, origin=None, origin_off=None,
+               page_bytes: int = PAGE_SIZE, stream=None):
+    """cc_read_merge_dev: the page-aligned reads (offsets, lengths) of a pool
+    with clone chunks, each answered from the written pages of the pool
+    (verified) and the never-written pages of its origin buffer: read i's
+    origin bytes start at origin[origin_off[i]] (`origin` a uint8 device
+    tensor, `origin_off` host integers, NO_ORIGIN = none).  Returns (out,
+    out_off, bad_per_read, bad_total, unwritten_per_read, unwritten_total):
+    `out` holds the reads' bytes back to back at `out_off` (int64 device
+    tensor); a never-written page with no origin leaves zeros there and shows
+    in the unwritten counts (PageNerverWrittenError).  Counts as read_snap's,
+    -1 in both = invalid read.  No host sync."""
+    import numpy as np
+    torch = _torch()
+    off = np.asarray(offsets, dtype=np.uint64)
+    ln = np.asarray(lengths, dtype=np.uint64)
+    if off.size != ln.size:
+        raise CurveCrcError(_lib.CC_EINVAL, "offsets/lengths size mismatch")
+    n = off.size
+    d_ooff = None
+    if origin is not None:
+        if origin_off is None:
+            raise CurveCrcError(_lib.CC_EINVAL, "origin needs origin_off")
+        o_off = np.asarray(origin_off, dtype=np.uint64)
+        if o_off.size != n:
+            raise CurveCrcError(_lib.CC_EINVAL, "origin_off size mismatch")
+    with _on_stream(stream):
+        bad = torch.zeros(max(n, 1), dtype=torch.int32, device=pool.device)
+        total = torch.zeros(1, dtype=torch.int64, device=pool.device)
+        unwritten = torch.zeros(max(n, 1), dtype=torch.int32, device=pool.device)
+        unwritten_total = torch.zeros(1, dtype=torch.int64, device=pool.device)
+        ends = np.cumsum(ln, dtype=np.uint64)
+        out = torch.zeros(int(ends[-1]) if n else 0, dtype=torch.uint8, device=pool.device)
+        out_off = torch.from_numpy((ends - ln).view(np.int64)).to(pool.device)
+        if n == 0:
+            return out, out_off, bad[:0], total, unwritten[:0], unwritten_total
+        rng = torch.from_numpy(np.stack([off, ln], axis=1).reshape(-1).view(np.int64)).to(pool.device)
+        if origin is not None:
+            d_ooff = torch.from_numpy(o_off.view(np.int64)).to(pool.device)
+        buf = out if out.numel() else torch.empty(4, dtype=torch.uint8, device=pool.device)  # never a NULL output
+    read_merge_records(pool, page_crcs, rng, n, clone, buf, out_off, bad, total, unwritten, unwritten_total,
+                       origin=origin, origin_off=d_ooff, page_bytes=page_bytes, stream=stream)
+    if stream is not None:
+        for t in (rng, buf, out_off, d_ooff, origin, bad, total, unwritten, unwritten_total):
+            if t is not None:
+                t.record_stream(stream)
+    return out, out_off, bad[:n], total, unwritten[:n], unwritten_total
+
+
+def _paste_fetched(pool, page_crcs, origin, dst_off, src_off, lens, clone, page_bytes, stream):
+    """clone_read's PasteCloneData step (inside clone_read the name `paste` is its enablePaste_ argument)."""
+    return paste(pool, page_crcs, origin, dst_off, src_off, lens, clone, page_bytes=page_bytes, stream=stream)
+
+
+def clone_read(pool, page_crcs, offsets, lengths, clone: Clone, fetch, paste: bool = True,
+               page_bytes: int = PAGE_SIZE, stream=None):
+    """CloneCore::HandleReadRequest for a batch (clone_core.cpp:165-194):
+    clone_check_reads; `fetch(indices)` ONCE for the reads that touch a
+    never-written page (numpy indices into the batch, ascending) -- the control
+    plane's download: it returns (origin uint8 device tensor, origin_off: one
+    byte offset per index); read_merge for all reads; and with paste=True
+    (enablePaste_) the fetched buffers are pasted over the same ranges
+    (PasteCloneData).  When no read needs its origin, fetch is not called and
+    nothing is pasted.  A read whose offset or length is no multiple of
+    page_bytes is never fetched or pasted (CloneReadByLocalInfo refuses it
+    before any download): read_merge marks it invalid.  Returns read_merge's
+    tuple.  One host sync, on `stream`: the check's counts choose what to
+    fetch."""
+    import numpy as np
+    off = np.asarray(offsets, dtype=np.uint64)
+    ln = np.asarray(lengths, dtype=np.uint64)
+    if off.size != ln.size:
+        raise CurveCrcError(_lib.CC_EINVAL, "offsets/lengths size mismatch")
+    counts, _ = clone_check_reads(pool, off, ln, clone, page_bytes=page_bytes, stream=stream)
+    if stream is not None:
+        stream.synchronize()  # the counts were made on `stream`; the copy below runs on the current one
+    counts = counts.cpu().numpy()
+    aligned = ((off | ln) & np.uint64(page_bytes - 1)) == 0
+    need = np.nonzero((counts > 0) & aligned)[0]  # -1 (past the pool): nothing to fetch, read_merge marks it
+    origin = o_off = None
+    if need.size:
+        origin, got = fetch(need)
+        got = np.asarray(got, dtype=np.uint64)
+        if got.size != need.size:
+            raise CurveCrcError(_lib.CC_EINVAL, "fetch must return one origin offset per index")
+        o_off = np.full(off.size, NO_ORIGIN, dtype=np.uint64)
+        o_off[need] = got
+    res = read_merge(pool, page_crcs, off, ln, clone, origin=origin, origin_off=o_off, page_bytes=page_bytes,
+                     stream=stream)
+    if paste and need.size:
+        if (ln[need] >> np.uint64(32)).any():
+            raise CurveCrcError(_lib.CC_EINVAL, "a paste entry holds at most 2^32 - 1 bytes")
+        _paste_fetched(pool, page_crcs, origin, off[need], o_off[need], ln[need], clone, page_bytes, stream)
+    return res
+
+
 def scan_files(paths, chunk_bytes: int = CHUNK_SIZE, meta_bytes: int = META_PAGE_SIZE,
                page_bytes: int = PAGE_SIZE, slice_bytes: int = SCAN_SIZE, io_threads: int = 0):
     """cc_scan_files: native pread + scan of chunk files.

@@ -2084,6 +2084,59 @@ int cc_clone_check_reads_dev(uint64_t pool_bytes, uint32_t page_bytes, const cc_
     return map_err(launch_clone_check(a, static_cast<hipStream_t>(stream)));
 }
 
+int cc_read_merge_dev(const void* d_pool, uint64_t pool_bytes, uint32_t page_bytes, const cc_range* d_reads,
+                      uint64_t n_reads, const uint32_t* d_page_crcs, const cc_clone* clone, const void* d_origin,
+                      const uint64_t* d_origin_off, uint64_t origin_bytes, void* d_out, const uint64_t* d_out_off,
+                      uint64_t out_bytes, uint32_t* d_bad_per_read, uint64_t* d_bad_total,
+                      uint32_t* d_unwritten_per_read, uint64_t* d_unwritten_total, void* stream) {
+    if (!log_page_ok(page_bytes)) return CC_EINVAL;
+    if (n_reads == 0) return CC_OK;
+    if (n_reads >= (1ull << 31)) return CC_EINVAL;
+    if (!d_pool || !d_reads || !d_page_crcs || !d_bad_per_read || !d_bad_total) return CC_EINVAL;
+    if (pool_bytes % page_bytes || ((uintptr_t)d_pool & 3u)) return CC_EINVAL;
+    if (!d_out || !d_out_off || ((uintptr_t)d_out & 3u)) return CC_EINVAL;  // no verify-only mode
+    if (!d_unwritten_per_read || !d_unwritten_total) return CC_EINVAL;
+    if (!clone || !clone->d_clone_slot || !clone->d_bitmap) return CC_EINVAL;  // d_claim is paste's alone
+    if (clone->chunk_bytes == 0 || clone->chunk_bytes % page_bytes || pool_bytes % clone->chunk_bytes) return CC_EINVAL;
+    if (d_origin && (!d_origin_off || ((uintptr_t)d_origin & 3u))) return CC_EINVAL;
+    CtxRef c;
+    int rc = get_ctx(&c);
+    if (rc) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    MergeReadLaunch a = {};
+    a.rv.pool = static_cast<const uint32_t*>(d_pool);
+    a.rv.pool_bytes = pool_bytes;
+    a.rv.page_bytes = page_bytes;
+    a.rv.page_shift = (uint32_t)__builtin_ctz(page_bytes);  // a power of two (log_page_ok)
+    a.rv.reads = reinterpret_cast<const RangeDesc*>(d_reads);
+    a.rv.n_reads = n_reads;
+    a.rv.page_crcs = d_page_crcs;
+    a.rv.bad_per_read = d_bad_per_read;
+    a.rv.bad_total = reinterpret_cast<unsigned long long*>(d_bad_total);
+    a.rv.image = c->image;
+    a.rv.kconst = kconst_for(page_bytes);
+    a.rv.blocks = c->cus;
+    a.geo = clone_geo(clone, page_bytes);
+    a.geo.claim = nullptr;  // never touched here
+    a.origin = static_cast<const unsigned char*>(d_origin);
+    a.origin_off = d_origin ? d_origin_off : nullptr;
+    a.origin_bytes = origin_bytes;
+    a.out = static_cast<unsigned char*>(d_out);
+    a.out_off = d_out_off;
+    a.out_bytes = out_bytes;
+    a.unwritten_per_read = d_unwritten_per_read;
+    a.unwritten_total = reinterpret_cast<unsigned long long*>(d_unwritten_total);
+    // the one-launch small path, on cc_verify_reads_dev's terms
+    if (n_reads <= 64 && pool_bytes / page_bytes < (1ull << 26)) return map_err(launch_merge_read_small(a, s));
+    return map_err(with_range_scratch(c.get(), s, 0,
+                                      [&](uint64_t* tiles, unsigned long long* tail, uint32_t*, uint32_t epoch) {
+                                          a.rv.tiles = tiles;
+                                          a.rv.tail = tail;
+                                          a.rv.epoch = epoch;
+                                          return launch_merge_read(a, s);
+                                      }));
+}
+
 // Streaming scan.  Each staging slot holds a batch of whole chunks (data and
 // metapages in separate device regions) plus the per-chunk results; a batch is
 // {H2D data+meta, page kernel over data, page kernel over metapages, fused

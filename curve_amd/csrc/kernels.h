@@ -361,6 +361,32 @@ struct CloneCheckLaunch {
     int blocks;                  // CUs
 };
 hipError_t launch_clone_check(const CloneCheckLaunch& a, hipStream_t s);
+// Clone reads (cc_read_merge_dev): snapshot reads' schedule over page-aligned
+// reads of a pool with clone chunks, every page slot resolved against its
+// chunk's written-page bitmap first.  A written page (no clone chunk, or its
+// bit set) is the live pool page: rehashed against page_crcs and stored at
+// out + out_off[read] + (page's position in the read).  A never-written page
+// (clone chunk, bit clear) counts on its read; when the read has an origin
+// (origin != null and origin_off[read] != kNoOrigin) the page's bytes are
+// origin + origin_off[read] + (page's position in the read), stored unhashed,
+// otherwise nothing of the page moves.  geo.claim is not used; geo.bitmap is
+// only read.  geo.n_slots == 0: every page is written and the tables are not read.
+constexpr uint64_t kNoOrigin = ~0ull;
+struct MergeReadLaunch {
+    ReadVerifyLaunch rv;            // pool, reads, page_crcs, bad counters, tiles, tail, epoch, image, grid
+    CloneGeo geo;
+    const unsigned char* origin;    // the fetched origin buffers, or null
+    const uint64_t* origin_off;     // [n_reads] byte offset of read i's origin bytes (kNoOrigin: none); null with origin
+    uint64_t origin_bytes;
+    unsigned char* out;
+    const uint64_t* out_off;        // [n_reads] byte offset of read i's bytes in out
+    uint64_t out_bytes;
+    uint32_t* unwritten_per_read;   // [n_reads] += never-written pages; UINT32_MAX for an invalid read
+    unsigned long long* unwritten_total;
+};
+hipError_t launch_merge_read(const MergeReadLaunch& a, hipStream_t s);
+// <= 64 reads in one launch (no tiles, no scratch)
+hipError_t launch_merge_read_small(const MergeReadLaunch& a, hipStream_t s);
 // CRC32C (butil Value) of arbitrary byte ranges of one device buffer, on the
 // flat block schedule, ONE launch: range_flat_kernel counts the
 // 4 KiB blocks of kRangeTiles contiguous tiles of the batch itself (epoch-tagged

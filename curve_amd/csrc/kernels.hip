@@ -3003,6 +3003,382 @@ __global__ __launch_bounds__(64 * kCloneWaves) void clone_check_kernel(CloneChec
     if (mine && lane == 0) atomicAdd(a.unwritten_total, (unsigned long long)mine);
 }
 
+// ---------------------------------------------------------------------------
+// Clone reads (cc_read_merge_dev): snap_read_kernel's schedule, every page
+// slot resolved against its chunk's written-page bitmap, the written pages
+// rehashed and delivered from the pool, the never-written ones delivered from
+// the read's fetched origin buffer.  Replaces the host loops of
+// CloneCore::ReadThenMerge (clone_core.cpp:352-416: Divide() into copied and
+// uncopied ranges, ReadChunk per copied range, cloneData->copy_to per uncopied
+// one).
+// ---------------------------------------------------------------------------
+// A read that is not served: misaligned, past the pool, an output range that
+// is unaligned or leaves the buffer, or -- with an origin (go != kNoOrigin) --
+// an origin range that is unaligned or leaves its buffer (len == 0 is valid).
+__device__ __forceinline__ bool merge_read_bad(const MergeReadLaunch& a, const RangeDesc& r, uint64_t oo, uint64_t go) {
+    if (!r.len) return false;
+    if ((r.off | r.len) & (uint64_t)(a.rv.page_bytes - 1u)) return true;
+    if (r.off >= a.rv.pool_bytes || r.len > a.rv.pool_bytes - r.off) return true;
+    if ((oo & 3u) || oo > a.out_bytes || r.len > a.out_bytes - oo) return true;
+    return go != kNoOrigin && ((go & 3u) || go > a.origin_bytes || r.len > a.origin_bytes - go);
+}
+__device__ __forceinline__ uint64_t merge_pages(const MergeReadLaunch& a, const RangeDesc& r, uint64_t oo, uint64_t go) {
+    return merge_read_bad(a, r, oo, go) ? 0u : read_pages(a.rv, r);
+}
+
+// Pages of tile t, uniform; mark: invalid reads get both of their words = UINT32_MAX
+// (the tile's counting wave marks them, as snap_tile_count does).
+__device__ __forceinline__ uint64_t merge_tile_count(const MergeReadLaunch& a, uint32_t t, uint32_t lane, bool mark) {
+    const uint64_t lo = a.rv.n_reads * t / kReadTiles, hi = a.rv.n_reads * (t + 1) / kReadTiles;
+    uint64_t sum = 0;
+    for (uint64_t i = lo + lane; i < hi; i += 64) {
+        const RangeDesc r = a.rv.reads[i];
+        const bool bad = merge_read_bad(a, r, a.out_off[i], a.origin ? a.origin_off[i] : kNoOrigin);
+        sum += bad ? 0u : read_pages(a.rv, r);
+        if (mark && bad) {
+            a.rv.bad_per_read[i] = 0xFFFFFFFFu;
+            a.unwritten_per_read[i] = 0xFFFFFFFFu;
+        }
+    }
+#pragma unroll
+    for (int d = 32; d; d >>= 1) sum += __shfl_xor(sum, d, 64);
+    return sum;
+}
+
+// One page slot on its way to its loads, resolved in the stages SnapPg goes
+// through: merge_slot_of (chunk, page in chunk, the chunk's bitmap slot),
+// merge_word_of (the slot's bitmap word), merge_unwritten (the bit, inverted:
+// a CLEAR bit of a clone chunk sends the page away from the pool).  Both table
+// words come in with vector loads of a uniform address and stay in a VGPR until
+// the next stage takes them a step later.
+struct MergePg {
+    uint64_t g;      // pool page
+    uint32_t owner;  // lane holding the page's read
+    uint32_t rel;    // the page's position in its read
+    uint32_t q;      // page in chunk
+    uint32_t s;      // the chunk's bitmap slot (>= n_slots: not a clone), once merge_word_of has taken it
+    uint32_t sv;     // VGPR: the slot as loaded
+    uint32_t wv;     // VGPR: the slot's bitmap word holding bit q, as loaded
+};
+__device__ __forceinline__ void merge_slot_of(const MergeReadLaunch& a, MergePg& p, uint32_t vz) {
+    p.q = 0;
+    p.s = 0xFFFFFFFFu;
+    p.sv = 0xFFFFFFFFu;
+    p.wv = 0xFFFFFFFFu;
+    if (!a.geo.n_slots) return;  // uniform: no clone chunk, nothing to resolve
+    const uint64_t c = clone_chunk_of(a.geo, p.g);
+    p.q = (uint32_t)(p.g - c * a.geo.pages_per_chunk);
+    p.sv = a.geo.clone_slot[c + vz];
+}
+__device__ __forceinline__ void merge_word_of(const MergeReadLaunch& a, MergePg& p, uint32_t vz) {
+    if (!a.geo.n_slots) return;
+    p.s = __builtin_amdgcn_readfirstlane(p.sv);
+    const uint32_t sc = p.s < a.geo.n_slots ? p.s : 0u;  // clamped: the same load every page
+    p.wv = a.geo.bitmap[(uint64_t)sc * a.geo.words_per_slot + (p.q >> 5) + vz];
+}
+__device__ __forceinline__ bool merge_unwritten(const MergeReadLaunch& a, const MergePg& p) {
+    if (!a.geo.n_slots) return false;
+    const uint32_t word = __builtin_amdgcn_readfirstlane(p.wv);
+    return p.s < a.geo.n_slots && !((word >> (p.q & 31u)) & 1u);
+}
+// A slot whose loads are out.  Its three outcomes, uniform: the live page
+// (stored CRC and page loaded: hash, compare, store), the origin's page (page
+// loaded: store), nothing (counted only).
+constexpr uint32_t kMergeLive = 0, kMergeOrigin = 1, kMergeNone = 2;
+struct MergeDst {
+    uint64_t out;    // the page's byte offset in the output
+    uint32_t owner;
+    uint32_t kind;
+    uint32_t crc;    // VGPR: the live page's stored CRC
+};
+__device__ __forceinline__ const uint32_t* merge_live_page(const MergeReadLaunch& a, uint64_t g) {
+    return a.rv.pool + (g << (a.rv.page_shift - 2u));
+}
+
+// The never-written pages of a wave's share come in runs of one read: a run is
+// held in two SGPRs and lands on its read with ONE lane-0 atomic when the next
+// read's first unwritten page arrives or the group of reads ends; the total
+// goes out once a wave.
+struct MergeRun {
+    uint32_t owner, count;  // uniform: the pending run's read (lane of the group) and its pages
+    uint64_t total;         // uniform: this wave's unwritten pages
+};
+__device__ __forceinline__ void merge_run_flush(const MergeReadLaunch& a, MergeRun& u, uint64_t base, uint32_t lane) {
+    if (!u.count) return;
+    if (lane == 0) atomicAdd(a.unwritten_per_read + base + u.owner, u.count);
+    u.total += u.count;
+    u.count = 0;
+}
+__device__ __forceinline__ void merge_run_add(const MergeReadLaunch& a, MergeRun& u, uint64_t base, uint32_t owner,
+                                              uint32_t lane) {
+    if (u.owner != owner) merge_run_flush(a, u, base, lane);
+    u.owner = owner;
+    u.count++;
+}
+
+// snap_read_kernel<M, true> with the clone resolution: the same tile counts,
+// shares, dynamic tail and three rotating register sets; the step that handles
+// page k first takes the table words loaded a step earlier, issues page k+3's
+// bitmap-word load and page k+4's slot load, and then page k+2's loads -- the
+// stored CRC and the pool page, the origin page, or none.  Lane j of a group
+// of 64 reads holds its read's output offset and its origin offset.
+template <int M>
+__global__ __launch_bounds__(64 * kRvWaves) void merge_read_kernel(MergeReadLaunch a) {
+    __shared__ uint32_t tab[kLdsBytes / 4];
+    const uint64_t n = a.rv.n_reads;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint64_t Wg = (uint64_t)gridDim.x * kRvWaves;
+    const uint64_t w = (uint64_t)blockIdx.x * kRvWaves + wave;
+    const uint64_t tag = (uint64_t)a.rv.epoch << kEpochShift;
+    for (uint64_t t = w; t < kReadTiles; t += Wg) {
+        const uint64_t cnt = merge_tile_count(a, (uint32_t)t, lane, true);
+        if (lane == 0) __hip_atomic_store(a.rv.tiles + t, tag | cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    unsigned long long* dyn_ctr = a.rv.tail + (a.rv.epoch & 1u) * kDynCtrWords64;
+    if (blockIdx.x == 0 && threadIdx.x < kRvHeads)
+        atomicExch(a.rv.tail + ((a.rv.epoch + 1u) & 1u) * kDynCtrWords64 + threadIdx.x * kDynHeadStride, 0ull);
+    fill_lds<64 * kRvWaves>(tab, static_cast<const uint4*>(a.rv.image));
+    const uint32_t c0 = lane << 2 & 0x7Cu;
+    const uint32_t c1 = c0 | 0x10000u;
+    const uint32_t cf = kFinBase + (lane << 2);
+    uint32_t vz = 0;
+    asm volatile("" : "+v"(vz));  // opaque zero: keeps uniform-address loads on the vector path
+
+    constexpr int kTpl = kReadTiles / 64;
+    uint64_t tb[kTpl];
+    wait_tiles<kTpl>(tb, a.rv.tiles, tag, lane, [&](uint32_t t) { return merge_tile_count(a, t, lane, false); });
+    uint64_t lsum = 0;
+#pragma unroll
+    for (int j = 0; j < kTpl; j++) lsum += tb[j];
+    const uint64_t cum = wave_scan_incl(lsum, lane);
+    const uint64_t T = readlane64(cum, 63);
+    const uint64_t Wt = (T + kRvMinSlots - 1) / kRvMinSlots;
+    const uint64_t W = Wt < Wg ? (Wt ? Wt : 1) : Wg;
+    if ((uint64_t)blockIdx.x * kRvWaves >= W) return;  // uniform per block: no share, no tail
+    const uint64_t Ts = T - T / kRvDynDiv;
+    uint32_t dyn_head, dyn_tried;
+    tail_cursor<kRvHeads>(dyn_head, dyn_tried);
+    uint64_t lo_slot = w < W ? Ts * w / W : Ts, hi_slot = w < W ? Ts * (w + 1) / W : Ts;  // waves past W: tail only
+    MergeRun run = {0u, 0u, 0ull};
+#pragma unroll 1
+    for (;;) {
+        uint64_t base = n, S = 0;
+        RangeDesc rs;
+        uint64_t os = 0, gs = kNoOrigin;
+        bool have_rs = false;
+        if (lo_slot < hi_slot) {
+            const TileHit th = tile_of(cum, tb, lo_slot, lane);
+            base = n * th.tile / kReadTiles;
+            S = th.before;
+            for (;;) {
+                const uint64_t ri = base + lane;
+                const uint64_t at = (ri < n ? ri : base) + vz;
+                rs = a.rv.reads[at];
+                os = a.out_off[at];
+                gs = a.origin ? a.origin_off[at] : kNoOrigin;
+                const uint64_t c = wave_scan_incl(ri < n ? merge_pages(a, rs, os, gs) : 0u, lane);
+                const uint64_t tot = readlane64(c, 63);
+                if (S + tot > lo_slot || base + 64 >= n) break;
+                S += tot;
+                base += 64;
+            }
+            have_rs = true;
+        }
+        for (; base < n && S < hi_slot; base += 64) {
+            const uint64_t ri = base + lane;
+            const bool valid = ri < n;
+            const uint64_t at = (valid ? ri : base) + vz;
+            const RangeDesc r = have_rs ? rs : a.rv.reads[at];
+            const uint64_t oo = have_rs ? os : a.out_off[at];
+            const uint64_t go = have_rs ? gs : a.origin ? a.origin_off[at] : kNoOrigin;
+            have_rs = false;
+            const uint32_t cnt = valid ? (uint32_t)merge_pages(a, r, oo, go) : 0u;  // 0 also for invalid reads
+            const uint64_t p0 = r.off >> a.rv.page_shift;
+            uint32_t cum32 = cnt;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const uint32_t o = __shfl_up(cum32, d, 64);
+                if (lane >= (uint32_t)d) cum32 += o;
+            }
+            const uint32_t P = __builtin_amdgcn_readlane(cum32, 63);
+            const uint32_t ks = lo_slot > S ? (uint32_t)(lo_slot - S) : 0u;
+            const uint32_t ke = hi_slot - S < (uint64_t)P ? (uint32_t)(hi_slot - S) : P;
+            S += P;
+            if (ks >= ke) continue;
+            // slot k (clamped to the share's last): its read's lane, its page, its chunk's bitmap slot
+            auto locate = [&](uint32_t k) {
+                k = k < ke ? k : ke - 1;
+                MergePg p;
+                p.owner = (uint32_t)__builtin_ctzll(__ballot(cum32 > k));
+                const uint32_t before = p.owner ? (uint32_t)__builtin_amdgcn_readlane(cum32, p.owner - 1) : 0u;
+                p.rel = k - before;
+                p.g = readlane64(p0, p.owner) + p.rel;
+                merge_slot_of(a, p, vz);
+                return p;
+            };
+            // the resolved page's outcome, output offset and loads; then the page
+            // behind it moves up: its bitmap word, and the slot of the one after
+            MergePg p3, p4;
+            auto issue = [&](uint32_t kn, uint32_t (&Y)[M], MergeDst& dy) {
+                const bool unwritten = merge_unwritten(a, p3);
+                const uint64_t from = readlane64(go, p3.owner);
+                const uint64_t in_read = (uint64_t)p3.rel << a.rv.page_shift;
+                const uint64_t g = p3.g;
+                dy.owner = p3.owner;
+                dy.kind = !unwritten ? kMergeLive : from != kNoOrigin ? kMergeOrigin : kMergeNone;
+                dy.out = readlane64(oo, p3.owner) + in_read;
+                dy.crc = 0;
+                p3 = p4;
+                merge_word_of(a, p3, vz);
+                p4 = locate(kn);
+                __builtin_amdgcn_sched_barrier(0);  // the table loads stay ahead of the page's
+                if (dy.kind == kMergeLive) {
+                    dy.crc = a.rv.page_crcs[g + vz];
+                    load_page<M>(Y, merge_live_page(a, g) + lane);
+                } else if (dy.kind == kMergeOrigin) {
+                    load_page<M>(Y, reinterpret_cast<const uint32_t*>(a.origin + from + in_read) + lane);
+                }
+            };
+            uint32_t A[M], B[M], Cq[M];
+            MergeDst dA, dB, dC;
+            p3 = locate(ks);
+            merge_word_of(a, p3, vz);
+            p4 = locate(ks + 1);
+            issue(ks + 2, A, dA);
+            issue(ks + 3, B, dB);
+            dC = dB;
+            // page k (registers X unless its outcome is none); page k+2's loads go into Y
+            auto step = [&](uint32_t (&X)[M], const MergeDst dx, uint32_t k, uint32_t (&Y)[M], MergeDst& dy) {
+                const bool more = k + 1 < ke;
+                issue(k + 4, Y, dy);
+                uint32_t* to = reinterpret_cast<uint32_t*>(a.out + dx.out) + lane;
+                if (dx.kind == kMergeLive) {
+                    const uint32_t crc = wave_xor(apply_fin(tab, chain<M>(tab, X, c0, c1), cf)) ^ a.rv.kconst;
+                    store_page<M>(X, to);
+                    if (crc != dx.crc && lane == 0) {
+                        atomicAdd(a.rv.bad_per_read + base + dx.owner, 1u);
+                        atomicAdd(a.rv.bad_total, 1ull);
+                    }
+                } else {
+                    if (dx.kind == kMergeOrigin) store_page<M>(X, to);
+                    merge_run_add(a, run, base, dx.owner, lane);
+                }
+                return more;
+            };
+            for (uint32_t k = ks;; k += 3) {
+                if (!step(A, dA, k, Cq, dC)) break;
+                if (!step(B, dB, k + 1, A, dA)) break;
+                if (!step(Cq, dC, k + 2, B, dB)) break;
+            }
+            merge_run_flush(a, run, base, lane);  // a run never outlives its group of reads
+        }
+        const uint64_t n_dyn = (T - Ts + kRvDynSlots - 1) / kRvDynSlots;
+        const uint64_t c = tail_pull<kRvHeads>(dyn_ctr, n_dyn, dyn_head, dyn_tried, lane);
+        if (c >= n_dyn) break;
+        lo_slot = Ts + c * kRvDynSlots;
+        hi_slot = lo_slot + kRvDynSlots < T ? lo_slot + kRvDynSlots : T;
+    }
+    if (run.total && lane == 0) atomicAdd(a.unwritten_total, (unsigned long long)run.total);
+}
+
+// <= 64 reads (one per lane) in ONE launch with no scratch, as
+// snap_read_small_kernel: every wave works out the batch's pages per read
+// (wave 0 of block 0 marks the invalid ones), the P pages are split evenly over
+// the fewest waves that give each >= kRvSmallMinSlots, and a wave resolves the
+// next page while it handles one.
+template <int M>
+__global__ __launch_bounds__(64 * kRvWaves) void merge_read_small_kernel(MergeReadLaunch a) {
+    __shared__ uint32_t tab[kLdsBytes / 4];
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    uint32_t vz = 0;
+    asm volatile("" : "+v"(vz));
+    const bool valid = lane < a.rv.n_reads;
+    const uint32_t at = (valid ? lane : 0u) + vz;
+    const RangeDesc r = a.rv.reads[at];
+    const uint64_t oo = a.out_off[at];
+    const uint64_t go = a.origin ? a.origin_off[at] : kNoOrigin;
+    const bool bad = merge_read_bad(a, r, oo, go);
+    const uint32_t cnt = valid && !bad ? (uint32_t)read_pages(a.rv, r) : 0u;
+    if (valid && bad && blockIdx.x == 0 && wave == 0) {
+        a.rv.bad_per_read[lane] = 0xFFFFFFFFu;
+        a.unwritten_per_read[lane] = 0xFFFFFFFFu;
+    }
+    const uint64_t p0 = r.off >> a.rv.page_shift;
+    uint32_t cum = cnt;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t o = __shfl_up(cum, d, 64);
+        if (lane >= (uint32_t)d) cum += o;
+    }
+    const uint32_t P = __builtin_amdgcn_readlane(cum, 63);
+    const uint32_t Wg = gridDim.x * kRvWaves, Wt = (P + kRvSmallMinSlots - 1) / kRvSmallMinSlots;
+    const uint32_t W = Wt < Wg ? Wt : Wg;
+    if (blockIdx.x * (uint32_t)kRvWaves >= W) return;  // uniform per block (P == 0: every block)
+    fill_lds<64 * kRvWaves>(tab, static_cast<const uint4*>(a.rv.image));
+    const uint32_t w = blockIdx.x * kRvWaves + wave;
+    if (w >= W) return;
+    const uint32_t k0 = (uint32_t)((uint64_t)P * w / W), k1 = (uint32_t)((uint64_t)P * (w + 1) / W);
+    if (k0 >= k1) return;
+    const uint32_t c0 = lane << 2 & 0x7Cu;
+    const uint32_t c1 = c0 | 0x10000u;
+    const uint32_t cf = kFinBase + (lane << 2);
+    auto locate = [&](uint32_t k) {
+        k = k < k1 ? k : k1 - 1;
+        MergePg p;
+        p.owner = (uint32_t)__builtin_ctzll(__ballot(cum > k));
+        const uint32_t before = p.owner ? (uint32_t)__builtin_amdgcn_readlane(cum, p.owner - 1) : 0u;
+        p.rel = k - before;
+        p.g = readlane64(p0, p.owner) + p.rel;
+        merge_slot_of(a, p, vz);
+        merge_word_of(a, p, vz);
+        return p;
+    };
+    auto issue = [&](const MergePg& p, uint32_t (&Y)[M], MergeDst& dy) {
+        const bool unwritten = merge_unwritten(a, p);
+        const uint64_t from = readlane64(go, p.owner);
+        const uint64_t in_read = (uint64_t)p.rel << a.rv.page_shift;
+        dy.owner = p.owner;
+        dy.kind = !unwritten ? kMergeLive : from != kNoOrigin ? kMergeOrigin : kMergeNone;
+        dy.out = readlane64(oo, p.owner) + in_read;
+        dy.crc = 0;
+        if (dy.kind == kMergeLive) {
+            dy.crc = a.rv.page_crcs[p.g + vz];
+            load_page<M>(Y, merge_live_page(a, p.g) + lane);
+        } else if (dy.kind == kMergeOrigin) {
+            load_page<M>(Y, reinterpret_cast<const uint32_t*>(a.origin + from + in_read) + lane);
+        }
+    };
+    // pages k0 .. k1-1, the next page's loads in flight while one is handled
+    uint32_t X[M], Y[M];
+    MergeDst dx, dy;
+    MergeRun run = {0u, 0u, 0ull};
+    issue(locate(k0), X, dx);
+    MergePg pn = locate(k0 + 1);
+    for (uint32_t k = k0; k < k1; k++) {
+        issue(pn, Y, dy);  // clamped: same loads every step
+        pn = locate(k + 2);
+        uint32_t* to = reinterpret_cast<uint32_t*>(a.out + dx.out) + lane;
+        if (dx.kind == kMergeLive) {
+            const uint32_t crc = wave_xor(apply_fin(tab, chain<M>(tab, X, c0, c1), cf)) ^ a.rv.kconst;
+            store_page<M>(X, to);
+            if (crc != dx.crc && lane == 0) {
+                atomicAdd(a.rv.bad_per_read + dx.owner, 1u);
+                atomicAdd(a.rv.bad_total, 1ull);
+            }
+        } else {
+            if (dx.kind == kMergeOrigin) store_page<M>(X, to);
+            merge_run_add(a, run, 0, dx.owner, lane);
+        }
+#pragma unroll
+        for (int j = 0; j < M; j++) X[j] = Y[j];
+        dx = dy;
+    }
+    merge_run_flush(a, run, 0, lane);
+    if (run.total && lane == 0) atomicAdd(a.unwritten_total, (unsigned long long)run.total);
+}
+
 __global__ void combine_kernel(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b, uint32_t m,
                                uint64_t n, uint32_t* __restrict__ out) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -3367,6 +3743,44 @@ hipError_t launch_clone_mark(const CloneMarkLaunch& a, hipStream_t s) {
 hipError_t launch_clone_check(const CloneCheckLaunch& a, hipStream_t s) {
     if (a.n == 0) return hipSuccess;
     hipLaunchKernelGGL(clone_check_kernel, clone_grid(a.n, a.blocks), dim3(64 * kCloneWaves), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_merge_read_small(const MergeReadLaunch& a, hipStream_t s) {
+    if (a.rv.n_reads == 0 || a.rv.n_reads > 64) return hipErrorInvalidValue;
+#define CC_MCASE(MM)                                                                                         \
+    case MM:                                                                                                 \
+        hipLaunchKernelGGL((merge_read_small_kernel<MM>), dim3(a.rv.blocks), dim3(64 * kRvWaves), 0, s, a);  \
+        break;
+    switch (a.rv.page_bytes / kWaveBytes) {
+        CC_MCASE(1)
+        CC_MCASE(2)
+        CC_MCASE(4)
+        CC_MCASE(8)
+        CC_MCASE(16)
+        CC_MCASE(32)
+        default: return hipErrorInvalidValue;
+    }
+#undef CC_MCASE
+    return hipGetLastError();
+}
+
+hipError_t launch_merge_read(const MergeReadLaunch& a, hipStream_t s) {
+    if (a.rv.n_reads == 0) return hipSuccess;
+#define CC_MCASE(MM)                                                                                   \
+    case MM:                                                                                           \
+        hipLaunchKernelGGL((merge_read_kernel<MM>), dim3(a.rv.blocks), dim3(64 * kRvWaves), 0, s, a);  \
+        break;
+    switch (a.rv.page_bytes / kWaveBytes) {
+        CC_MCASE(1)
+        CC_MCASE(2)
+        CC_MCASE(4)
+        CC_MCASE(8)
+        CC_MCASE(16)
+        CC_MCASE(32)
+        default: return hipErrorInvalidValue;
+    }
+#undef CC_MCASE
     return hipGetLastError();
 }
 

@@ -453,8 +453,9 @@ int cc_read_snap_dev(const void* d_pool, uint64_t pool_bytes, uint32_t page_byte
 /* Clone chunks: the written-page bitmap on the device.  A clone chunk is
  * allocated lazily (clone, or recover from a snapshot in S3 or another volume)
  * and carries, in its metapage, one bit per page that has been written; the
- * three calls below are the three places where CSChunkFile looks at or changes
- * that bitmap, for a pool some of whose chunks are clones.  A clone chunk can
+ * first three calls below are the three places where CSChunkFile looks at or
+ * changes that bitmap, for a pool some of whose chunks are clones, and
+ * cc_read_merge_dev is CloneCore's read of such a chunk.  A clone chunk can
  * never open a snapshot (Write returns StatusConflictError,
  * chunkserver_chunkfile.cpp:329-336), so these calls and cc_apply_log_cow_dev
  * never meet on one chunk.
@@ -559,13 +560,84 @@ int cc_clone_mark_dev(uint64_t pool_bytes, uint32_t page_bytes, const cc_update*
  * that lie in a clone chunk with a clear bit (the caller zeroes it),
  * *d_unwritten_total += their sum; UINT32_MAX marks a read that runs past the
  * pool; len == 0 touches nothing.  A non-zero count is the reference's
- * PageNerverWrittenError, or "fetch the origin and cc_paste_dev it"; a read
- * with count 0 may go to cc_verify_reads_dev or cc_read_snap_dev.  It reads
+ * PageNerverWrittenError, or "fetch the origin, answer with cc_read_merge_dev
+ * and cc_paste_dev it"; a read with count 0 may go to cc_verify_reads_dev,
+ * cc_read_snap_dev or cc_read_merge_dev.  It reads
  * bitmap words only, in one launch.  Checks as cc_paste_dev's where they
  * apply, with d_reads and both counters non-NULL and n_reads < 2^31. */
 int cc_clone_check_reads_dev(uint64_t pool_bytes, uint32_t page_bytes, const cc_range* d_reads, uint64_t n_reads,
                              const cc_clone* clone, uint32_t* d_unwritten_per_read, uint64_t* d_unwritten_total,
                              void* stream);
+
+/* Clone reads: a batch of CloneCore::ReadThenMerge calls (clone_core.cpp:352-416:
+ * Divide() the request's blocks into copied and uncopied ranges, ReadChunk per
+ * copied range, cloneData->copy_to per uncopied one), fed as
+ * SetReadChunkResponse feeds them -- the read of a clone chunk answered from
+ * the written pages of the pool and the unwritten pages of the fetched origin
+ * buffer, in ONE gathered, verified call.  It sits between
+ * cc_clone_check_reads_dev (which reads must fetch their origin) and
+ * cc_paste_dev (the optional, asynchronous PasteCloneData): the answer never
+ * waits for the paste.
+ *
+ * Reads follow cc_read_snap_dev's conventions: pool byte ranges whose off and
+ * len are multiples of page_bytes (CloneReadByLocalInfo refuses anything else,
+ * clone_core.cpp:145-157); a read may cross chunk boundaries, and every page is
+ * resolved on its own.  `clone` is cc_paste_dev's struct; the call reads
+ * d_clone_slot and d_bitmap only, never touches d_claim or d_pasted (both may
+ * be NULL) and writes no bitmap.  For pool page p of read i, chunk c = p /
+ * pages_per_chunk, q = p % pages_per_chunk and s = d_clone_slot[c]:
+ *
+ * WRITTEN -- s >= n_slots (not a clone, out-of-range values included) or bit q
+ * of slot s set: the bytes are the live pool page, rehashed whole and compared
+ * with d_page_crcs[p]; a mismatch adds 1 to d_bad_per_read[i] and to
+ * *d_bad_total; the bytes go to d_out + d_out_off[i] + (page start - off_i)
+ * whether or not they matched (cc_read_snap_dev's rule).
+ *
+ * NEVER WRITTEN -- s < n_slots and bit q clear: the pool page and its CRC word
+ * are not read; d_unwritten_per_read[i] and *d_unwritten_total each get +1
+ * (the caller zeroes them).  If the read has an origin (d_origin != NULL and
+ * d_origin_off[i] != CC_NO_ORIGIN) the page's bytes are d_origin +
+ * d_origin_off[i] + (page start - off_i), stored at the same output position
+ * UNHASHED: the origin has no stored CRC to check against, and the reference
+ * returns it as downloaded.  If the read has no origin the output bytes of
+ * that page are left untouched; a non-zero count on such a read is the
+ * reference's PageNerverWrittenError.
+ *
+ * Every page is judged by the bitmaps as they stood before the call (the call
+ * writes none), so the result does not depend on the schedule.  d_out must not
+ * alias d_pool or d_origin, and no cc_paste_dev, cc_clone_mark_dev or write
+ * log may run over the same chunks and bitmaps on another stream at the same
+ * time.  Overlapping output ranges are the caller's business.
+ *
+ * A read is INVALID -- both of its words = UINT32_MAX, nothing hashed, nothing
+ * written -- when its off or len is misaligned, when it runs past the pool,
+ * when d_out_off[i] is not 4-byte aligned or d_out_off[i] + len > out_bytes,
+ * or, for a read with an origin, when d_origin_off[i] is not 4-byte aligned or
+ * d_origin_off[i] + len > origin_bytes (a read with CC_NO_ORIGIN never looks
+ * at the origin buffer, whatever its size).  Nothing is ever written outside
+ * [d_out, d_out + out_bytes).  len == 0 is valid: it touches nothing and
+ * leaves its words alone.
+ *
+ * Checked before a device is needed (CC_EINVAL): cc_read_snap_dev's checks on
+ * page_bytes, pool_bytes, d_pool, d_reads, d_page_crcs, d_bad_per_read,
+ * d_bad_total and n_reads; d_out and d_out_off non-NULL and d_out 4-byte
+ * aligned (there is no verify-only mode: cc_verify_reads_dev and
+ * cc_read_snap_dev cover it); both unwritten counters non-NULL; clone, its
+ * d_clone_slot and its d_bitmap non-NULL, chunk_bytes a multiple of page_bytes
+ * that divides pool_bytes; d_origin non-NULL with a NULL d_origin_off, or not
+ * 4-byte aligned.  n_reads == 0 is CC_OK.  No GPU: CC_ENODEV, never a CPU
+ * fallback.
+ *
+ * ONE launch on cc_read_snap_dev's schedule and scratch; a batch of <= 64
+ * reads on a pool of < 2^26 pages takes one launch with no scratch at all.
+ * The unwritten pages of one read that fall to one wave are counted with one
+ * atomic. */
+#define CC_NO_ORIGIN 0xFFFFFFFFFFFFFFFFull
+int cc_read_merge_dev(const void* d_pool, uint64_t pool_bytes, uint32_t page_bytes, const cc_range* d_reads,
+                      uint64_t n_reads, const uint32_t* d_page_crcs, const cc_clone* clone, const void* d_origin,
+                      const uint64_t* d_origin_off, uint64_t origin_bytes, void* d_out, const uint64_t* d_out_off,
+                      uint64_t out_bytes, uint32_t* d_bad_per_read, uint64_t* d_bad_total,
+                      uint32_t* d_unwritten_per_read, uint64_t* d_unwritten_total, void* stream);
 
 /* One chunk file as the datastore holds it: metapage + data
  * (file = metapage || data, chunkserver_chunkfile.cpp:497-536). */
