@@ -106,6 +106,12 @@ class CcClone(ctypes.Structure):
 CC_NOT_CLONE = 0xFFFFFFFF
 CC_NO_ORIGIN = 0xFFFFFFFFFFFFFFFF  # cc_read_merge_dev: d_origin_off[i] of a read with no origin
 
+
+class CcRepairCounts(ctypes.Structure):
+    """cc_repair_counts (include/curve_crc.h): entry i's pages by class after cc_repair_dev."""
+    _fields_ = [("clean", _u32), ("repaired", _u32), ("failed", _u32), ("shadowed", _u32)]
+
+
 SIGNATURES = {
     "crc32c_value": (_u32, [_vp, _sz]),
     "crc32c_extend": (_u32, [_u32, _vp, _sz]),
@@ -165,6 +171,7 @@ SIGNATURES = {
     "cc_clone_check_reads_dev": (_int, [_u64, _u32, _vp, _u64, ctypes.POINTER(CcClone), _vp, _vp, _vp]),
     "cc_read_merge_dev": (_int, [_vp, _u64, _u32, _vp, _u64, _vp, ctypes.POINTER(CcClone), _vp, _vp, _u64, _vp, _vp,
                                  _u64, _vp, _vp, _vp, _vp, _vp]),
+    "cc_repair_dev": (_int, [_vp, _u64, _u32, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cc_comm_unique_id": (_int, [_vp, _sz]),
     "cc_comm_init": (_int, [ctypes.POINTER(_vp), _int, _int, _vp, _sz]),
     "cc_comm_init_timeout": (_int, [ctypes.POINTER(_vp), _int, _int, _vp, _sz, _u32]),

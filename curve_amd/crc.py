@@ -1100,6 +1100,125 @@ def clone_read(pool, page_crcs, offsets, lengths, clone: Clone, fetch, paste: bo
     return res
 
 
+REPAIR_CLEAN, REPAIR_REPAIRED, REPAIR_FAILED, REPAIR_SHADOWED = 0, 1, 2, 3  # the words of cc_repair_counts, in order
+REPAIR_CLASSES = ("clean", "repaired", "failed", "shadowed")
+
+
+def repair_claim(pool, page_bytes: int = PAGE_SIZE):
+    """cc_repair_dev's claim table for `pool`: one int32 per pool page, -1
+    (all-ones) everywhere, which is how every completed call leaves it.  Keep it
+    beside the pool and hand it to every repair call on it."""
+    torch = _torch()
+    nb = _nbytes(pool)
+    if nb % page_bytes:
+        raise CurveCrcError(_lib.CC_EINVAL, "pool size is not a multiple of page_bytes")
+    return torch.full((nb // page_bytes,), -1, dtype=torch.int32, device=pool.device)
+
+
+def repair_records(pool, page_crcs, src, d_reqs, n: int, claim, per_entry, expect=None, totals=None,
+                   page_bytes: int = PAGE_SIZE, stream=None):
+    """cc_repair_dev on a batch already resident on the device: `d_reqs` =
+    device tensor of n cc_update records (log_records), an ORDERED batch: entry
+    i offers src[src_i + ...] as the candidate for the pool pages of [dst_i,
+    dst_i + len_i).  The lowest-indexed valid entry naming a page handles it:
+    with e = expect[p] (or page_crcs[p] when expect is None) the page is clean
+    (the live bytes hash to e), repaired (the candidate does: it is stored, and
+    page_crcs[p] = e) or failed (neither: nothing written); every other pair is
+    shadowed.  `per_entry` int32 [n, 4] gets += by class (clean, repaired,
+    failed, shadowed; -1 in all four marks an invalid entry), `totals` int64
+    [4] (optional) the sums; `claim` = repair_claim(pool).  No host sync."""
+    torch = _torch()
+    if claim.numel() * page_bytes < _nbytes(pool) or claim.element_size() != 4:
+        raise CurveCrcError(_lib.CC_EINVAL, "claim must hold one 32-bit word per pool page")
+    if page_crcs.numel() * page_bytes < _nbytes(pool) or page_crcs.element_size() != 4:
+        raise CurveCrcError(_lib.CC_EINVAL, "page_crcs must hold one 32-bit CRC per pool page")
+    if expect is not None and (expect.numel() * page_bytes < _nbytes(pool) or expect.element_size() != 4):
+        raise CurveCrcError(_lib.CC_EINVAL, "expect must hold one 32-bit CRC per pool page")
+    if per_entry.numel() < 4 * n or per_entry.element_size() != 4:
+        raise CurveCrcError(_lib.CC_EINVAL, "per_entry must hold four 32-bit words per entry")
+    if totals is not None and (totals.numel() < 4 or totals.element_size() != 8):
+        raise CurveCrcError(_lib.CC_EINVAL, "totals must hold four 64-bit words")
+    with torch.cuda.device(pool.device):
+        check(lib().cc_repair_dev(_dev_ptr(pool, "pool"), _nbytes(pool), page_bytes, _dev_ptr(src, "src"),
+                                  _nbytes(src), _dev_ptr(d_reqs, "reqs"), n, _dev_ptr(page_crcs, "page_crcs"),
+                                  _dev_ptr(expect, "expect") if expect is not None else None,
+                                  _dev_ptr(claim, "claim"), _dev_ptr(per_entry, "per_entry"),
+                                  _dev_ptr(totals, "totals") if totals is not None else None,
+                                  _stream_handle(stream)), "cc_repair_dev")
+    if stream is not None:
+        for t in (claim, expect, totals):
+            if t is not None:
+                t.record_stream(stream)
+
+
+def repair(pool, page_crcs, src, dst_off, src_off, lens, claim, expect=None, page_bytes: int = PAGE_SIZE,
+           stream=None):
+    """cc_repair_dev: the candidate ranges (dst_off, src_off, lens), in order,
+    from the device tensor `src` (a peer's copies) for `pool`.  Returns
+    (per_entry int32 [n, 4] device tensor: each entry's pages as clean,
+    repaired, failed, shadowed, -1 in all four = invalid entry; totals int64
+    [4]).  No host sync."""
+    import numpy as np
+    torch = _torch()
+    rec = log_records(dst_off, src_off, lens)
+    n = rec.size
+    with _on_stream(stream):
+        per_entry = torch.zeros((max(n, 1), 4), dtype=torch.int32, device=pool.device)
+        totals = torch.zeros(4, dtype=torch.int64, device=pool.device)
+        if n == 0:
+            return per_entry[:0], totals
+        d_reqs = torch.from_numpy(rec.view(np.uint8)).to(pool.device)
+    repair_records(pool, page_crcs, src, d_reqs, n, claim, per_entry, expect=expect, totals=totals,
+                   page_bytes=page_bytes, stream=stream)
+    if stream is not None:
+        for t in (d_reqs, per_entry, totals, src):
+            t.record_stream(stream)
+    return per_entry[:n], totals
+
+
+def repair_pages(pool, page_crcs, pages, fetchers, claim, expect=None, page_bytes: int = PAGE_SIZE, stream=None):
+    """Repair the pool pages `pages` (page indices, any order, duplicates
+    allowed) from a list of peers, in the spirit of clone_read.  The pages are
+    made unique and ascending; then for each fetcher in order
+    `fetch(remaining_pages)` -- the control plane's ReadChunk from that peer --
+    returns (src uint8 device tensor, src_off: one byte offset per page), and
+    ONE repair call sends one one-page entry per remaining page, so every
+    entry's counts are a status.  Pages still failed go to the next fetcher; the
+    rounds stop when none is left.  Returns (pages, cls, by): the unique
+    ascending pages (numpy int64), each page's final class (numpy int8:
+    REPAIR_CLEAN, REPAIR_REPAIRED or REPAIR_FAILED) and the index of the fetcher
+    whose copy repaired it (numpy int64, -1 unless repaired).  With no fetcher
+    nothing is judged and every page stays REPAIR_FAILED.  A page beyond the
+    pool or a fetched range outside its buffer raises CC_EINVAL (the earlier
+    rounds' repairs stand).  One host sync a round, on `stream`: the statuses
+    choose what the next peer is asked for."""
+    import numpy as np
+    pg = np.unique(np.asarray(pages, dtype=np.int64))
+    cls = np.full(pg.size, REPAIR_FAILED, dtype=np.int8)
+    by = np.full(pg.size, -1, dtype=np.int64)
+    left = np.arange(pg.size)
+    for f, fetch in enumerate(fetchers):
+        if not left.size:
+            break
+        src, got = fetch(pg[left])
+        got = np.asarray(got, dtype=np.uint64)
+        if got.size != left.size:
+            raise CurveCrcError(_lib.CC_EINVAL, "fetch must return one source offset per page")
+        dst = pg[left].astype(np.uint64) * np.uint64(page_bytes)
+        per, _ = repair(pool, page_crcs, src, dst, got, np.full(left.size, page_bytes, np.uint32), claim,
+                        expect=expect, page_bytes=page_bytes, stream=stream)
+        if stream is not None:
+            stream.synchronize()  # the statuses were made on `stream`; the copy below runs on the current one
+        st = per.cpu().numpy().reshape(-1, 4)
+        if (st < 0).any():
+            raise CurveCrcError(_lib.CC_EINVAL, "a page lies beyond the pool or its fetched range outside the buffer")
+        now = st[:, :3].argmax(axis=1).astype(np.int8)  # unique pages: nothing is shadowed, one word is 1
+        cls[left] = now
+        by[left[now == REPAIR_REPAIRED]] = f
+        left = left[now == REPAIR_FAILED]
+    return pg, cls, by
+
+
 def scan_files(paths, chunk_bytes: int = CHUNK_SIZE, meta_bytes: int = META_PAGE_SIZE,
                page_bytes: int = PAGE_SIZE, slice_bytes: int = SCAN_SIZE, io_threads: int = 0):
     """cc_scan_files: native pread + scan of chunk files.

@@ -2041,6 +2041,48 @@ int cc_paste_dev(void* d_pool, uint64_t pool_bytes, uint32_t page_bytes, const v
                                       }));
 }
 
+int cc_repair_dev(void* d_pool, uint64_t pool_bytes, uint32_t page_bytes, const void* d_src, uint64_t src_bytes,
+                  const cc_update* d_reqs, uint64_t n, uint32_t* d_page_crcs, const uint32_t* d_expect,
+                  uint32_t* d_claim, cc_repair_counts* d_per_entry, uint64_t* d_totals, void* stream) {
+    static_assert(sizeof(cc_repair_counts) == 16, "four words an entry");
+    if (!log_page_ok(page_bytes)) return CC_EINVAL;
+    if (n == 0) return CC_OK;
+    if (n >= (1ull << 31)) return CC_EINVAL;  // entry indices live in d_claim, all-ones reserved
+    if (!d_pool || !d_src || !d_reqs || !d_page_crcs || !d_claim || !d_per_entry) return CC_EINVAL;
+    if (pool_bytes % page_bytes || ((uintptr_t)d_pool & 3u) || ((uintptr_t)d_src & 3u)) return CC_EINVAL;
+    CtxRef c;
+    int rc = get_ctx(&c);
+    if (rc) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    RepairLaunch a = {};
+    a.pool = static_cast<uint32_t*>(d_pool);
+    a.pool_bytes = pool_bytes;
+    a.page_bytes = page_bytes;
+    a.page_shift = (uint32_t)__builtin_ctz(page_bytes);  // a power of two (log_page_ok)
+    a.src = static_cast<const unsigned char*>(d_src);
+    a.src_bytes = src_bytes;
+    a.reqs = reinterpret_cast<const UpdateDesc*>(d_reqs);
+    a.n = n;
+    a.page_crcs = d_page_crcs;
+    a.expect = d_expect;
+    a.claim = d_claim;
+    a.per_entry = reinterpret_cast<uint32_t*>(d_per_entry);
+    a.totals = reinterpret_cast<unsigned long long*>(d_totals);
+    a.image = c->image;
+    a.kconst = kconst_for(page_bytes);
+    a.blocks = c->cus;
+    // the claim launch also marks the invalid entries
+    hipError_t e = launch_repair_claim(a, s);
+    if (e != hipSuccess) return map_err(e);
+    return map_err(with_range_scratch(c.get(), s, 0,
+                                      [&](uint64_t* tiles, unsigned long long* tail, uint32_t*, uint32_t epoch) {
+                                          a.tiles = tiles;
+                                          a.tail = tail;
+                                          a.epoch = epoch;
+                                          return launch_repair(a, s);
+                                      }));
+}
+
 int cc_clone_mark_dev(uint64_t pool_bytes, uint32_t page_bytes, const cc_update* d_log, uint64_t n_updates,
                       uint32_t max_len, const cc_clone* clone, void* stream) {
     if (!log_page_ok(page_bytes)) return CC_EINVAL;

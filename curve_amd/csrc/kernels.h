@@ -387,6 +387,40 @@ struct MergeReadLaunch {
 hipError_t launch_merge_read(const MergeReadLaunch& a, hipStream_t s);
 // <= 64 reads in one launch (no tiles, no scratch)
 hipError_t launch_merge_read_small(const MergeReadLaunch& a, hipStream_t s);
+// Page repair (cc_repair_dev): an ORDERED batch of candidate ranges in two
+// launches, as cc_paste_dev.  The claim launch leaves in claim[p] the lowest
+// index of the valid entries naming pool page p (and marks the invalid
+// entries); the repair launch walks the batch's (entry, page) slots on
+// verify-on-read's schedule.  The slot that finds its own index in claim[p]
+// handles the page: it hashes the live page against e = expect ? expect[p] :
+// page_crcs[p]; when that misses it loads and hashes the candidate and stores
+// it when it hits; it counts the page on its entry by class and resets the
+// claim word.  Every other slot
+// is shadowed: no page traffic, no hash, one count a run.
+constexpr uint32_t kRepairClean = 0, kRepairRepaired = 1, kRepairFailed = 2, kRepairShadowed = 3;
+struct RepairLaunch {
+    uint32_t* pool;
+    uint64_t pool_bytes;
+    uint32_t page_bytes;
+    uint32_t page_shift;         // log2(page_bytes)
+    const unsigned char* src;
+    uint64_t src_bytes;
+    const UpdateDesc* reqs;
+    uint64_t n;
+    uint32_t* page_crcs;
+    const uint32_t* expect;      // [pool pages] the authority's CRCs, or null: page_crcs is the record
+    uint32_t* claim;             // [pool pages], all 0xFFFFFFFF between calls
+    uint32_t* per_entry;         // [n][4] += entry i's pages by class; all four UINT32_MAX for an invalid entry
+    unsigned long long* totals;  // [4] += the four sums, or null
+    uint64_t* tiles;             // the stream's range scratch, as ReadVerifyLaunch
+    unsigned long long* tail;
+    uint32_t epoch;
+    const void* image;
+    uint32_t kconst;
+    int blocks;                  // CUs
+};
+hipError_t launch_repair_claim(const RepairLaunch& a, hipStream_t s);
+hipError_t launch_repair(const RepairLaunch& a, hipStream_t s);
 // CRC32C (butil Value) of arbitrary byte ranges of one device buffer, on the
 // flat block schedule, ONE launch: range_flat_kernel counts the
 // 4 KiB blocks of kRangeTiles contiguous tiles of the batch itself (epoch-tagged

@@ -3379,6 +3379,278 @@ __global__ __launch_bounds__(64 * kRvWaves) void merge_read_small_kernel(MergeRe
     if (run.total && lane == 0) atomicAdd(a.unwritten_total, (unsigned long long)run.total);
 }
 
+// ---------------------------------------------------------------------------
+// Page repair (cc_repair_dev): a peer's copy of a page enters the pool only
+// when it hashes to the CRC on record.  A sibling of the paste pair above: the
+// same ordered batch of UpdateDesc entries, the same claim launch, the same
+// (entry, page) slots on verify-on-read's schedule; the gate is a hash
+// comparison where paste's is a bitmap bit, and the claim table is indexed by
+// pool page (there are no chunks here).
+// ---------------------------------------------------------------------------
+// An entry that cc_repair_dev skips whole: cc_paste_dev's rule (paste_bad).
+__device__ __forceinline__ bool repair_bad(const RepairLaunch& a, const UpdateDesc& u) {
+    if (!u.len) return false;
+    if ((u.dst | u.len) & (uint64_t)(a.page_bytes - 1u)) return true;
+    if (u.dst >= a.pool_bytes || u.len > a.pool_bytes - u.dst) return true;
+    return (u.src & 3u) || u.src > a.src_bytes || u.len > a.src_bytes - u.src;
+}
+__device__ __forceinline__ uint32_t repair_pages(const RepairLaunch& a, const UpdateDesc& u) {
+    return repair_bad(a, u) ? 0u : u.len >> a.page_shift;
+}
+
+// Launch 1 of cc_repair_dev: every (valid entry, page) pair bids for its page
+// with its entry index; the lowest index holds the claim word when the launch
+// ends.  The lane that loads an invalid entry marks its four count words.
+// Moves no page and reads no table.
+__global__ __launch_bounds__(64 * kCloneWaves) void repair_claim_kernel(RepairLaunch a) {
+    const uint32_t lane = threadIdx.x & 63u;
+    clone_entry_pages(
+        a.n, lane,
+        [&](uint64_t i, uint64_t& p0, uint64_t& cnt) {
+            const UpdateDesc u = a.reqs[i];
+            if (repair_bad(a, u)) {
+                for (int j = 0; j < 4; j++) a.per_entry[4 * i + j] = 0xFFFFFFFFu;
+                return;
+            }
+            p0 = u.dst >> a.page_shift;
+            cnt = u.len >> a.page_shift;
+        },
+        [&](uint64_t e, uint64_t page) { atomicMin(a.claim + page, (uint32_t)e); });
+}
+
+// Pages of tile t of the repair batch, uniform (paste_tile_count's twin).
+__device__ __forceinline__ uint64_t repair_tile_count(const RepairLaunch& a, uint32_t t, uint32_t lane) {
+    const uint64_t lo = a.n * t / kReadTiles, hi = a.n * (t + 1) / kReadTiles;
+    uint64_t sum = 0;
+    for (uint64_t i = lo + lane; i < hi; i += 64) sum += repair_pages(a, a.reqs[i]);
+#pragma unroll
+    for (int d = 32; d; d >>= 1) sum += __shfl_xor(sum, d, 64);
+    return sum;
+}
+
+// One (entry, page) slot of the repair launch on its way to its loads: located
+// (its entry's lane, its pool page) with the page's claim word loaded at once,
+// by a vector load of a uniform address that stays in a VGPR until the slot's
+// loads are issued two steps later.
+struct RepairPg {
+    uint64_t g;      // pool page
+    uint32_t owner;  // lane holding the page's entry
+    uint32_t rel;    // the page's position in its entry
+    uint32_t cv;     // VGPR: the page's claim word as loaded
+};
+// A slot whose loads are out: the page it handles when it holds the claim.
+struct RepairDst {
+    uint64_t g;
+    uint64_t from;   // the candidate page's byte offset in the source
+    uint32_t owner;
+    uint32_t ev;     // VGPR: the CRC on record for the page (expect[g], or page_crcs[g])
+    bool win;
+};
+
+// The shadowed slots of a wave's share come in runs of one entry (an entry
+// whose pages all belong to lower-indexed ones): MergeRun's scheme, the run in
+// two SGPRs and ONE lane-0 atomic on the entry's fourth word when the next
+// entry's first shadowed slot arrives or the group of entries ends.
+struct RepairRun {
+    uint32_t owner, count;  // uniform: the pending run's entry (lane of the group) and its slots
+    uint64_t total;         // uniform: this wave's shadowed slots
+};
+__device__ __forceinline__ void repair_run_flush(const RepairLaunch& a, RepairRun& u, uint64_t base, uint32_t lane) {
+    if (!u.count) return;
+    if (lane == 0) atomicAdd(a.per_entry + 4 * (base + u.owner) + kRepairShadowed, u.count);
+    u.total += u.count;
+    u.count = 0;
+}
+__device__ __forceinline__ void repair_run_add(const RepairLaunch& a, RepairRun& u, uint64_t base, uint32_t owner,
+                                               uint32_t lane) {
+    if (u.owner != owner) repair_run_flush(a, u, base, lane);
+    u.owner = owner;
+    u.count++;
+}
+
+// Launch 2 of cc_repair_dev, on paste_kernel's schedule (tile counts published
+// by the waves, shares at slot granularity, 1/16 dynamic tail) over the batch's
+// (entry, page) slots.  The slot whose claim word equals its own entry index
+// handles the page: the CRC on record and the live page are loaded two steps
+// ahead (the table word before the page) and the page is hashed as it passes
+// through the registers.  Only when it misses the record is the candidate page
+// loaded, there and then, and hashed, and stored when it hits (measured: the
+// other waves of the CU hide that wait, and a clean page costs one page read
+// instead of two; DESIGN 6b "Page repair").  The lane-0 epilogue mends the
+// CRC word, counts the page on its entry by class and puts 0xFFFFFFFF back
+// into the claim word.  Every other
+// slot is shadowed: no page load, no hash, counted a run at a time.  A loser
+// may read the claim word before or after the winner's reset: neither value is
+// its own index (paste_kernel's comment), so no third launch is needed.  Only
+// the page's handler reads or writes the page and its CRC word, so every page
+// is judged by the pool as it stood before the call.
+template <int M>
+__global__ __launch_bounds__(64 * kRvWaves) void repair_kernel(RepairLaunch a) {
+    __shared__ uint32_t tab[kLdsBytes / 4];
+    const uint64_t n = a.n;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint64_t Wg = (uint64_t)gridDim.x * kRvWaves;
+    const uint64_t w = (uint64_t)blockIdx.x * kRvWaves + wave;
+    const uint64_t tag = (uint64_t)a.epoch << kEpochShift;
+    for (uint64_t t = w; t < kReadTiles; t += Wg) {
+        const uint64_t cnt = repair_tile_count(a, (uint32_t)t, lane);
+        if (lane == 0) __hip_atomic_store(a.tiles + t, tag | cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    unsigned long long* dyn_ctr = a.tail + (a.epoch & 1u) * kDynCtrWords64;
+    if (blockIdx.x == 0 && threadIdx.x < kRvHeads)
+        atomicExch(a.tail + ((a.epoch + 1u) & 1u) * kDynCtrWords64 + threadIdx.x * kDynHeadStride, 0ull);
+    fill_lds<64 * kRvWaves>(tab, static_cast<const uint4*>(a.image));
+    const uint32_t c0 = lane << 2 & 0x7Cu;
+    const uint32_t c1 = c0 | 0x10000u;
+    const uint32_t cf = kFinBase + (lane << 2);
+    uint32_t vz = 0;
+    asm volatile("" : "+v"(vz));  // opaque zero: keeps uniform-address loads on the vector path
+    const uint32_t* record = a.expect ? a.expect : a.page_crcs;
+
+    constexpr int kTpl = kReadTiles / 64;
+    uint64_t tb[kTpl];
+    wait_tiles<kTpl>(tb, a.tiles, tag, lane, [&](uint32_t t) { return repair_tile_count(a, t, lane); });
+    uint64_t lsum = 0;
+#pragma unroll
+    for (int j = 0; j < kTpl; j++) lsum += tb[j];
+    const uint64_t cum = wave_scan_incl(lsum, lane);
+    const uint64_t T = readlane64(cum, 63);
+    const uint64_t Wt = (T + kRvMinSlots - 1) / kRvMinSlots;
+    const uint64_t W = Wt < Wg ? (Wt ? Wt : 1) : Wg;
+    if ((uint64_t)blockIdx.x * kRvWaves >= W) return;  // uniform per block: no share, no tail
+    const uint64_t Ts = T - T / kRvDynDiv;
+    uint32_t dyn_head, dyn_tried;
+    tail_cursor<kRvHeads>(dyn_head, dyn_tried);
+    uint64_t lo_slot = w < W ? Ts * w / W : Ts, hi_slot = w < W ? Ts * (w + 1) / W : Ts;  // waves past W: tail only
+    uint32_t nclean = 0, nrepaired = 0, nfailed = 0;  // uniform: this wave's handled pages, added to the totals once
+    RepairRun run = {0u, 0u, 0ull};
+#pragma unroll 1
+    for (;;) {
+        uint64_t base = n, S = 0;
+        UpdateDesc us;
+        bool have_us = false;
+        if (lo_slot < hi_slot) {
+            const TileHit th = tile_of(cum, tb, lo_slot, lane);
+            base = n * th.tile / kReadTiles;
+            S = th.before;
+            for (;;) {
+                const uint64_t ei = base + lane;
+                us = a.reqs[(ei < n ? ei : base) + vz];
+                const uint64_t c = wave_scan_incl(ei < n ? repair_pages(a, us) : 0u, lane);
+                const uint64_t tot = readlane64(c, 63);
+                if (S + tot > lo_slot || base + 64 >= n) break;
+                S += tot;
+                base += 64;
+            }
+            have_us = true;
+        }
+        for (; base < n && S < hi_slot; base += 64) {
+            const uint64_t ei = base + lane;
+            const bool valid = ei < n;
+            const UpdateDesc u = have_us ? us : a.reqs[(valid ? ei : base) + vz];
+            have_us = false;
+            const uint32_t cnt = valid ? repair_pages(a, u) : 0u;  // 0 also for invalid entries
+            const uint64_t p0 = u.dst >> a.page_shift;
+            const uint64_t so = u.src;
+            uint32_t cum32 = cnt;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const uint32_t o = __shfl_up(cum32, d, 64);
+                if (lane >= (uint32_t)d) cum32 += o;
+            }
+            const uint32_t P = __builtin_amdgcn_readlane(cum32, 63);
+            const uint32_t ks = lo_slot > S ? (uint32_t)(lo_slot - S) : 0u;
+            const uint32_t ke = hi_slot - S < (uint64_t)P ? (uint32_t)(hi_slot - S) : P;
+            S += P;
+            if (ks >= ke) continue;
+            // slot k (clamped to the share's last): its entry's lane, its page, and the page's claim word on its way
+            auto locate = [&](uint32_t k) {
+                k = k < ke ? k : ke - 1;
+                RepairPg p;
+                p.owner = (uint32_t)__builtin_ctzll(__ballot(cum32 > k));
+                const uint32_t before = p.owner ? (uint32_t)__builtin_amdgcn_readlane(cum32, p.owner - 1) : 0u;
+                p.rel = k - before;
+                p.g = readlane64(p0, p.owner) + p.rel;
+                p.cv = a.claim[p.g + vz];
+                return p;
+            };
+            // the located slot: does it hold its page's claim?  Then the slot
+            // behind it moves up, and the winner's record word and live page are loaded
+            RepairPg p3, p4;
+            auto issue = [&](uint32_t kn, uint32_t (&Y)[M], RepairDst& dy) {
+                const uint32_t holder = __builtin_amdgcn_readfirstlane(p3.cv);
+                dy.g = p3.g;
+                dy.owner = p3.owner;
+                dy.win = holder == (uint32_t)base + p3.owner;
+                dy.ev = 0;
+                dy.from = readlane64(so, p3.owner) + ((uint64_t)p3.rel << a.page_shift);
+                p3 = p4;
+                p4 = locate(kn);
+                if (dy.win) dy.ev = record[dy.g + vz];
+                __builtin_amdgcn_sched_barrier(0);  // the table loads stay ahead of the page's
+                if (dy.win) load_page<M>(Y, a.pool + (dy.g << (a.page_shift - 2u)) + lane);
+            };
+            // slot k (registers X when it won); the loads of slot k + 2 go into Y
+            auto step = [&](uint32_t (&X)[M], const RepairDst dx, uint32_t k, uint32_t (&Y)[M], RepairDst& dy) {
+                const bool more = k + 1 < ke;
+                issue(k + 4, Y, dy);
+                if (dx.win) {
+                    const uint32_t live = wave_xor(apply_fin(tab, chain<M>(tab, X, c0, c1), cf)) ^ a.kconst;
+                    const uint32_t e = __builtin_amdgcn_readfirstlane(dx.ev);
+                    uint32_t cls = kRepairClean;
+                    if (live == e) {
+                        nclean++;
+                    } else {  // the candidate, now: X is free to take it
+                        load_page<M>(X, reinterpret_cast<const uint32_t*>(a.src + dx.from) + lane);
+                        const uint32_t cand = wave_xor(apply_fin(tab, chain<M>(tab, X, c0, c1), cf)) ^ a.kconst;
+                        if (cand == e) {
+                            cls = kRepairRepaired;
+                            nrepaired++;
+                            store_page<M>(X, a.pool + (dx.g << (a.page_shift - 2u)) + lane);
+                        } else {
+                            cls = kRepairFailed;
+                            nfailed++;
+                        }
+                    }
+                    if (lane == 0) {
+                        if (cls == kRepairRepaired || (cls == kRepairClean && a.expect)) a.page_crcs[dx.g] = e;
+                        atomicAdd(a.per_entry + 4 * (base + dx.owner) + cls, 1u);
+                        __hip_atomic_store(a.claim + dx.g, 0xFFFFFFFFu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    }
+                } else {
+                    repair_run_add(a, run, base, dx.owner, lane);
+                }
+                return more;
+            };
+            uint32_t A[M], B[M], Cq[M];
+            RepairDst dA, dB, dC;
+            p3 = locate(ks);
+            p4 = locate(ks + 1);
+            issue(ks + 2, A, dA);
+            issue(ks + 3, B, dB);
+            dC = dB;
+            for (uint32_t k = ks;; k += 3) {
+                if (!step(A, dA, k, Cq, dC)) break;
+                if (!step(B, dB, k + 1, A, dA)) break;
+                if (!step(Cq, dC, k + 2, B, dB)) break;
+            }
+            repair_run_flush(a, run, base, lane);  // a run never outlives its group of entries
+        }
+        const uint64_t n_dyn = (T - Ts + kRvDynSlots - 1) / kRvDynSlots;
+        const uint64_t c = tail_pull<kRvHeads>(dyn_ctr, n_dyn, dyn_head, dyn_tried, lane);
+        if (c >= n_dyn) break;
+        lo_slot = Ts + c * kRvDynSlots;
+        hi_slot = lo_slot + kRvDynSlots < T ? lo_slot + kRvDynSlots : T;
+    }
+    if (lane == 0 && a.totals) {
+        if (nclean) atomicAdd(a.totals + kRepairClean, (unsigned long long)nclean);
+        if (nrepaired) atomicAdd(a.totals + kRepairRepaired, (unsigned long long)nrepaired);
+        if (nfailed) atomicAdd(a.totals + kRepairFailed, (unsigned long long)nfailed);
+        if (run.total) atomicAdd(a.totals + kRepairShadowed, (unsigned long long)run.total);
+    }
+}
+
 __global__ void combine_kernel(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b, uint32_t m,
                                uint64_t n, uint32_t* __restrict__ out) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -3781,6 +4053,31 @@ hipError_t launch_merge_read(const MergeReadLaunch& a, hipStream_t s) {
         default: return hipErrorInvalidValue;
     }
 #undef CC_MCASE
+    return hipGetLastError();
+}
+
+hipError_t launch_repair_claim(const RepairLaunch& a, hipStream_t s) {
+    if (a.n == 0) return hipSuccess;
+    hipLaunchKernelGGL(repair_claim_kernel, clone_grid(a.n, a.blocks), dim3(64 * kCloneWaves), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_repair(const RepairLaunch& a, hipStream_t s) {
+    if (a.n == 0) return hipSuccess;
+#define CC_FCASE(MM)                                                                               \
+    case MM:                                                                                       \
+        hipLaunchKernelGGL((repair_kernel<MM>), dim3(a.blocks), dim3(64 * kRvWaves), 0, s, a);     \
+        break;
+    switch (a.page_bytes / kWaveBytes) {
+        CC_FCASE(1)
+        CC_FCASE(2)
+        CC_FCASE(4)
+        CC_FCASE(8)
+        CC_FCASE(16)
+        CC_FCASE(32)
+        default: return hipErrorInvalidValue;
+    }
+#undef CC_FCASE
     return hipGetLastError();
 }
 

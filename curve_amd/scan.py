@@ -149,6 +149,35 @@ class DevicePool:
         pages = sorted(int(p) for p in lst[:n].cpu().tolist())
         return [(p // ppc, p % ppc) for p in pages]
 
+    def repair_bad_pages(self, expected_page_crcs, fetchers, max_bad: int = 4096, claim=None, stream=None):
+        """Detect, fetch, install only what verifies, verify again: bad_pages
+        against `expected_page_crcs` (the authority's table, or this pool's own),
+        C.repair_pages of those pages from `fetchers` in order with
+        expect=expected_page_crcs (each `fetch(pool page indices)` returns (src
+        device tensor, one byte offset per page) -- a peer's ReadChunk), and a
+        second page_verify of the whole pool.  self.page_crcs is mended where a
+        page is clean or repaired.  Returns (repaired, still_bad): repaired =
+        [(chunk index, page in chunk, fetcher index)], still_bad = [(chunk
+        index, page in chunk)] for the pages no peer could mend, both sorted;
+        the second verify's count must equal len(still_bad) (CC_ECORRUPT
+        otherwise: the pool changed under the repair).  `claim` =
+        C.repair_claim(self.data), made here when None."""
+        ppc = self.chunk_size // self.page_bytes
+        with C._on_stream(stream):  # the counts are read back on the stream that made them
+            bad = self.bad_pages(expected_page_crcs, max_bad=max_bad, stream=stream)
+            if not bad:
+                return [], []
+            if claim is None:
+                claim = C.repair_claim(self.data, self.page_bytes)
+            pages, cls, by = C.repair_pages(self.data, self.page_crcs, [c * ppc + q for c, q in bad], fetchers, claim,
+                                            expect=expected_page_crcs, page_bytes=self.page_bytes, stream=stream)
+            left = int(C.page_verify(self.data, expected_page_crcs, self.page_bytes, stream=stream)[0])
+        repaired = [(int(p) // ppc, int(p) % ppc, int(f)) for p, k, f in zip(pages, cls, by) if k == C.REPAIR_REPAIRED]
+        still = [(int(p) // ppc, int(p) % ppc) for p, k in zip(pages, cls) if k == C.REPAIR_FAILED]
+        if left != len(still):
+            raise C.CurveCrcError(-74, f"{left} bad pages after the repair, {len(still)} expected")
+        return repaired, still
+
     # -- reference surfaces built on the device results ----------------------
     def scan_maps(self, logical_pool_id: int, copyset_id: int, first_index: int = 0) -> List[ScanMap]:
         """ScanMaps as ScanChunkRequest::OnApply builds them (op_request.cpp:795-803),
@@ -202,6 +231,9 @@ class DevicePool:
         after = torch.tensor(list(after_bytes), dtype=torch.int64, device=dev)
         grp = torch.tensor(list(group), dtype=torch.int32, device=dev)
         return C.digest_dev(self.file_crcs, after, grp, n_groups, stream=stream)
+
+
+ChunkPool = DevicePool  # the pool of chunk files under its other name
 
 
 def scan_copyset_dir(data_dir: str, logical_pool_id: int, copyset_id: int, first_index: int = 0,

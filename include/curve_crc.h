@@ -639,6 +639,76 @@ int cc_read_merge_dev(const void* d_pool, uint64_t pool_bytes, uint32_t page_byt
                       uint64_t out_bytes, uint32_t* d_bad_per_read, uint64_t* d_bad_total,
                       uint32_t* d_unwritten_per_read, uint64_t* d_unwritten_total, void* stream);
 
+/* Page repair: a peer's copy of a page enters the pool ONLY if it hashes to the
+ * CRC on record.  The reference detects and stops: ScanManager::CompareMap puts
+ * the failed maps into failedScanMaps_ (scan_manager.cpp:397) and the heartbeat
+ * reports them (heartbeat.cpp:158); the integrity calls here name the bad page
+ * (cc_page_verify_list_dev, cc_integrity_check).  This call closes the loop for
+ * two situations.  SCRUB REPAIR: a page's bytes no longer match
+ * d_page_crcs[p]; a peer's copy is fetched and accepted only when it hashes to
+ * the stored CRC (d_expect == NULL).  REPLICA RESYNC: a follower's CRC table
+ * differs from the authority's (the leader's, or the majority's) in some pages;
+ * those pages are fetched from the authority, each is accepted only when it
+ * hashes to the AUTHORITY's CRC, and the local table word is brought to that
+ * value (d_expect = the authority's table).
+ *
+ * d_reqs[0..n) is an ORDERED batch of cc_update entries: entry i offers
+ * d_src + src_i + (page start - dst_i) as the candidate for every pool page in
+ * [dst_i, dst_i + len_i).  A pool page named by several valid entries is
+ * handled by the LOWEST-indexed one; every other (entry, page) pair is
+ * SHADOWED: it moves no bytes and hashes nothing.  (A second peer for a page
+ * that failed is tried by sending the page again in a later call.)
+ *
+ * For the handling entry, with e = d_expect ? d_expect[p] : d_page_crcs[p] and
+ * the pool as it stood BEFORE the call (only the handler reads or writes the
+ * page and its CRC word):
+ *   CLEAN     the live page hashes to e.  No pool byte is written; with
+ *             d_expect, d_page_crcs[p] becomes e (a stale table word is mended).
+ *   REPAIRED  otherwise, when the candidate hashes to e: the candidate's bytes
+ *             are stored to the pool page and d_page_crcs[p] = e.
+ *   FAILED    neither hashes to e: neither the page nor its CRC word is written.
+ * So afterwards every clean or repaired page hashes to e and d_page_crcs[p] ==
+ * e, and a failed or shadowed-only page is bit for bit what it was.  The pool,
+ * the table, the counts and the claim table do not depend on the schedule.
+ *
+ * d_per_entry[i] gets += 1 in the word of its class for each of entry i's
+ * pages (the caller zeroes it): for a valid entry the four words sum to
+ * len_i / page_bytes, and for an entry of one page they are a status.
+ * d_totals, when non-NULL, gets += the four sums in the struct's order.
+ *
+ * An entry is INVALID -- all four of its words = UINT32_MAX, nothing claimed,
+ * hashed or written -- when dst or len is not a multiple of page_bytes, when
+ * it runs past the pool (dst >= pool_bytes or len > pool_bytes - dst), when src
+ * is not 4-byte aligned or when src + len > src_bytes.  len == 0 is valid: it
+ * touches nothing and leaves its words alone.  d_src must not alias d_pool.
+ *
+ * Checked before a device is needed (CC_EINVAL): page_bytes = 256 * 2^k
+ * (k = 0..5); pool_bytes whole pages; d_pool and d_src 4-byte aligned; d_pool,
+ * d_src, d_reqs, d_page_crcs, d_claim and d_per_entry non-NULL; n < 2^31 (entry
+ * indices live in d_claim, all-ones reserved).  n == 0 is CC_OK.  No GPU:
+ * CC_ENODEV, never a CPU fallback.
+ *
+ * d_claim is the call's scratch, one word per POOL PAGE, kept by the caller:
+ * all 0xFFFFFFFF before the first call, and every call that completes leaves
+ * it so.  Two launches on `stream`, as cc_paste_dev.  CLAIM: one lane per
+ * (valid entry, page) does atomicMin(d_claim[p], i); it moves no page traffic
+ * and also marks the invalid entries.  REPAIR: every (entry, page) pair is one
+ * slot on verify-on-read's schedule (the slots split evenly over the device,
+ * the last 1/16 dynamically, using the stream's range scratch the engine keeps:
+ * no caller work buffer); the slot that finds its own index in d_claim[p] loads
+ * and hashes the live page; only when that misses e does it load and hash the
+ * candidate, and store it when it hits; it counts and puts 0xFFFFFFFF back.  A
+ * shadowed slot reads either the handler's index or all-ones, never its own, so
+ * no third launch is needed; shadowed slots are counted a run at a time.  The
+ * caller must not run another call that writes the same pages, table words or
+ * claim words on another stream at the same time. */
+typedef struct cc_repair_counts {
+    uint32_t clean, repaired, failed, shadowed;
+} cc_repair_counts;
+int cc_repair_dev(void* d_pool, uint64_t pool_bytes, uint32_t page_bytes, const void* d_src, uint64_t src_bytes,
+                  const cc_update* d_reqs, uint64_t n, uint32_t* d_page_crcs, const uint32_t* d_expect,
+                  uint32_t* d_claim, cc_repair_counts* d_per_entry, uint64_t* d_totals, void* stream);
+
 /* One chunk file as the datastore holds it: metapage + data
  * (file = metapage || data, chunkserver_chunkfile.cpp:497-536). */
 typedef struct cc_chunk_src {
