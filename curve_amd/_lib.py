@@ -162,6 +162,8 @@ SIGNATURES = {
     "cc_apply_logs_work_bytes": (_u64, [_u64, _u32, _u32]),
     "cc_page_list_probe_dev": (_int, [_vp, _u64, _vp, _u64, _vp, _vp]),
     "cc_apply_logs_dev": (_int, [_vp, _u64, _u32, _vp, _u32, _u32, _vp, _int, _vp, _u64, _vp]),
+    "cc_apply_logs_cow_dev": (_int, [_vp, _u64, _u32, _vp, _u32, _u32, _vp, _int, _vp, _u64, _vp,
+                                     ctypes.POINTER(CcCow), ctypes.POINTER(CcClone)]),
     "cc_verify_reads_work_bytes": (_u64, [_u64]),
     "cc_verify_reads_dev": (_int, [_vp, _u64, _u32, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _vp]),
     "cc_read_snap_dev": (_int, [_vp, _u64, _u32, _vp, _u64, _vp, ctypes.POINTER(CcCow), _vp, _vp, _u64, _vp, _vp,

@@ -609,11 +609,14 @@ def page_list_probe(pool, d_pages, n: int, out, stream=None):
 
 
 def apply_logs(pool, page_crcs, batches, max_len: int, page_bytes: int = PAGE_SIZE, stream=None,
-               delta: bool = False):
+               delta: bool = False, cow: Optional["Cow"] = None, clone: Optional["Clone"] = None):
     """cc_apply_logs_dev: a QUEUE of write logs applied in order -- the same
     pool bytes and page CRCs as one apply_log call per batch, pipelined (each
     batch's page kernel also groups the next batch's pieces).  `batches`: a
-    list of (src, d_log, n_updates) -- device tensors as for apply_log."""
+    list of (src, d_log, n_updates) -- device tensors as for apply_log.
+    With `cow` and/or `clone` it is cc_apply_logs_cow_dev: one pass before the
+    queue leaves the snapshot slots and the clone bitmaps as apply_log_cow +
+    clone_mark per batch would (page_crcs must hold the CRCs before the queue)."""
     import ctypes
     torch = _torch()
     if not batches:
@@ -634,11 +637,29 @@ def apply_logs(pool, page_crcs, batches, max_len: int, page_bytes: int = PAGE_SI
         arr[i].d_log = _dev_ptr(d_log, "log").value if int(n) else None
         arr[i].n_updates = int(n)
     with torch.cuda.device(pool.device):
-        check(lib().cc_apply_logs_dev(_dev_ptr(pool, "pool"), _nbytes(pool), page_bytes, ctypes.cast(arr, ctypes.c_void_p),
-                                      len(batches), max_len, _dev_ptr(page_crcs, "page_crcs"), 1 if delta else 0,
-                                      _dev_ptr(work, "work"), work.numel(), _stream_handle(stream)), "cc_apply_logs_dev")
+        if cow is None and clone is None:
+            check(lib().cc_apply_logs_dev(_dev_ptr(pool, "pool"), _nbytes(pool), page_bytes,
+                                          ctypes.cast(arr, ctypes.c_void_p), len(batches), max_len,
+                                          _dev_ptr(page_crcs, "page_crcs"), 1 if delta else 0, _dev_ptr(work, "work"),
+                                          work.numel(), _stream_handle(stream)), "cc_apply_logs_dev")
+        else:
+            ws = cow.struct() if cow is not None else None
+            ls = clone.struct() if clone is not None else None
+            check(lib().cc_apply_logs_cow_dev(_dev_ptr(pool, "pool"), _nbytes(pool), page_bytes,
+                                              ctypes.cast(arr, ctypes.c_void_p), len(batches), max_len,
+                                              _dev_ptr(page_crcs, "page_crcs"), 1 if delta else 0,
+                                              _dev_ptr(work, "work"), work.numel(), _stream_handle(stream),
+                                              ctypes.byref(ws) if ws is not None else None,
+                                              ctypes.byref(ls) if ls is not None else None), "cc_apply_logs_cow_dev")
     if stream is not None:
         work.record_stream(stream)
+        if cow is not None:
+            _record_cow(cow, stream)
+            for t in (cow.copied, cow.stale):
+                if t is not None:
+                    t.record_stream(stream)
+        if clone is not None:
+            _record_clone(clone, stream)
     return 1
 
 

@@ -1671,10 +1671,72 @@ uint64_t cc_apply_logs_work_bytes(uint64_t max_updates, uint32_t max_len, uint32
     return logs_work(max_updates, max_len, page_bytes, &w) ? w.bytes : 0;
 }
 
-int cc_apply_logs_dev(void* d_pool, uint64_t pool_bytes, uint32_t page_bytes, const cc_log_batch* batches,
-                      uint32_t n_batches, uint32_t max_len, uint32_t* d_page_crcs, int delta, void* d_work,
-                      uint64_t work_bytes, void* stream) {
+namespace {
+bool clone_ok(const cc_clone* cl, uint64_t pool_bytes, uint32_t page_bytes);
+CloneGeo clone_geo(const cc_clone* cl, uint32_t page_bytes);
+
+// cc_apply_logs_cow_dev's pass before the queue's own launches: the pairs of
+// every non-empty batch, kPrepassBatches descriptors a launch.
+hipError_t logs_prepass(DevCtx* c, hipStream_t s, const unsigned char* d_pool, uint64_t pool_bytes, uint32_t page_bytes,
+                        const cc_log_batch* batches, uint32_t n_batches, uint32_t max_len, const uint32_t* d_page_crcs,
+                        const cc_cow* cow, const cc_clone* clone) {
+    LogsPrepassLaunch a = {};
+    a.pool = d_pool;
+    a.pool_bytes = pool_bytes;
+    a.page_bytes = page_bytes;
+    a.page_shift = (uint32_t)__builtin_ctz(page_bytes);  // a power of two (log_page_ok)
+    a.max_len = max_len;
+    a.slots = log_slots(max_len, page_bytes);
+    if (cow) {
+        a.pages_per_chunk = cow->chunk_bytes / page_bytes;
+        a.words_per_slot = (a.pages_per_chunk + 31u) / 32u;
+        a.n_slots = cow->n_slots;
+        a.snap_slot = cow->d_snap_slot;
+        a.snap = static_cast<unsigned char*>(cow->d_snap);
+        a.snap_crcs = cow->d_snap_crcs;
+        a.snap_bitmap = cow->d_snap_bitmap;
+        a.page_crcs = d_page_crcs;
+        a.copied = reinterpret_cast<unsigned long long*>(cow->d_copied);
+        a.stale = reinterpret_cast<unsigned long long*>(cow->d_stale);
+    }
+    if (clone) a.clone = clone_geo(clone, page_bytes);
+    a.image = c->image;
+    a.kconst = kconst_for(page_bytes);
+    auto flush = [&]() {
+        // a lane per pair up to one workgroup per CU (the rehash fills the CU's LDS), two without it
+        const uint64_t wb = (a.n_pairs + 64u * kPrepassWaves - 1) / (64u * kPrepassWaves);
+        const uint64_t cap = (uint64_t)c->cus * (a.stale ? 1u : 2u);
+        a.blocks = (int)(wb < cap ? wb : cap);
+        const hipError_t e = launch_logs_prepass(a, s);
+        a.n_batches = 0;
+        a.n_pairs = 0;
+        return e;
+    };
+    for (uint32_t k = 0; k < n_batches; k++) {
+        if (batches[k].n_updates == 0) continue;
+        LogsPrepassBatch& b = a.b[a.n_batches++];
+        b.upd = reinterpret_cast<const UpdateDesc*>(batches[k].d_log);
+        b.n_pairs = batches[k].n_updates * a.slots;
+        b.pair0 = a.n_pairs;
+        a.n_pairs += b.n_pairs;
+        if (a.n_batches == (uint32_t)kPrepassBatches) {
+            const hipError_t e = flush();
+            if (e != hipSuccess) return e;
+        }
+    }
+    return a.n_batches ? flush() : hipSuccess;
+}
+
+int apply_logs(void* d_pool, uint64_t pool_bytes, uint32_t page_bytes, const cc_log_batch* batches, uint32_t n_batches,
+               uint32_t max_len, uint32_t* d_page_crcs, int delta, void* d_work, uint64_t work_bytes, void* stream,
+               const cc_cow* cow, const cc_clone* clone) {
     if (!log_page_ok(page_bytes)) return CC_EINVAL;
+    if (cow) {  // apply_log's checks: a malformed struct is refused even for an empty queue
+        if (cow->chunk_bytes == 0 || cow->chunk_bytes % page_bytes || pool_bytes % cow->chunk_bytes) return CC_EINVAL;
+        if (!cow->d_snap_slot || !cow->d_snap || !cow->d_snap_crcs || !cow->d_snap_bitmap) return CC_EINVAL;
+        if ((uintptr_t)cow->d_snap & 3u) return CC_EINVAL;
+    }
+    if (clone && !clone_ok(clone, pool_bytes, page_bytes)) return CC_EINVAL;  // cc_clone_mark_dev's
     if (n_batches == 0) return CC_OK;
     if (!batches || !d_pool || !d_page_crcs || !d_work || max_len == 0) return CC_EINVAL;
     if (pool_bytes % page_bytes || ((uintptr_t)d_pool & 3u)) return CC_EINVAL;
@@ -1683,6 +1745,7 @@ int cc_apply_logs_dev(void* d_pool, uint64_t pool_bytes, uint32_t page_bytes, co
     for (uint32_t k = 0; k < n_batches; k++) {
         const cc_log_batch& b = batches[k];
         if (b.n_updates && (!b.d_log || !b.d_src || ((uintptr_t)b.d_src & 3u))) return CC_EINVAL;
+        if (clone && b.n_updates >= (1ull << 31)) return CC_EINVAL;  // cc_clone_mark_dev's
         max_n = b.n_updates > max_n ? b.n_updates : max_n;
     }
     if (max_n == 0) return CC_OK;
@@ -1719,6 +1782,11 @@ int cc_apply_logs_dev(void* d_pool, uint64_t pool_bytes, uint32_t page_bytes, co
     hipError_t e;
     DevCtx::LogTable* t = log_table(c.get(), s, 2 * W.table_entries, &e);  // two tables: its halves
     if (e != hipSuccess) return map_err(e);
+    // snapshots and clone marks: one pass over the whole queue, before its first write
+    if ((cow || clone) &&
+        (e = logs_prepass(c.get(), s, static_cast<const unsigned char*>(d_pool), pool_bytes, page_bytes, batches,
+                          n_batches, max_len, d_page_crcs, cow, clone)) != hipSuccess)
+        return map_err(e);
     if (!t) {  // no engine table for this stream (kMaxTailBlocks streams hold one, or a huge log): one call a batch
         lk.unlock();
         for (uint32_t k = 0; k < n_batches; k++)
@@ -1817,6 +1885,21 @@ int cc_apply_logs_dev(void* d_pool, uint64_t pool_bytes, uint32_t page_bytes, co
     }
     if (e != hipSuccess) t->dirty = true;  // a launch may have run in part: clear the engine table before its next use
     return map_err(e);
+}
+}  // namespace
+
+int cc_apply_logs_dev(void* d_pool, uint64_t pool_bytes, uint32_t page_bytes, const cc_log_batch* batches,
+                      uint32_t n_batches, uint32_t max_len, uint32_t* d_page_crcs, int delta, void* d_work,
+                      uint64_t work_bytes, void* stream) {
+    return apply_logs(d_pool, pool_bytes, page_bytes, batches, n_batches, max_len, d_page_crcs, delta, d_work,
+                      work_bytes, stream, nullptr, nullptr);
+}
+
+int cc_apply_logs_cow_dev(void* d_pool, uint64_t pool_bytes, uint32_t page_bytes, const cc_log_batch* batches,
+                          uint32_t n_batches, uint32_t max_len, uint32_t* d_page_crcs, int delta, void* d_work,
+                          uint64_t work_bytes, void* stream, const cc_cow* cow, const cc_clone* clone) {
+    return apply_logs(d_pool, pool_bytes, page_bytes, batches, n_batches, max_len, d_page_crcs, delta, d_work,
+                      work_bytes, stream, cow, clone);
 }
 
 int cc_page_list_probe_dev(const void* d_pool, uint64_t pool_bytes, const uint64_t* d_pages, uint64_t n,

@@ -349,6 +349,48 @@ struct CloneMarkLaunch {
     int blocks;                  // CUs
 };
 hipError_t launch_clone_mark(const CloneMarkLaunch& a, hipStream_t s);
+// cc_apply_logs_cow_dev: the copy-on-write pass and the clone marks of a whole
+// QUEUE of write logs in one launch BEFORE the queue's own kernels (a snapshot
+// keeps a page's first version, and the first batch that touches a page finds
+// it as it stood before the queue).  Up to kPrepassBatches batch descriptors
+// ride in the kernel argument: no host-to-device copy, no allocation.  One lane
+// is one (entry, page slot) pair, `slots` pairs an entry as the insert kernel
+// counts its pieces; pair0 is the batch's first pair in the launch.
+constexpr int kPrepassBatches = 32;
+constexpr int kPrepassWaves = 16;  // waves per workgroup of logs_prepass_kernel<M, Verify>
+struct LogsPrepassBatch {
+    const UpdateDesc* upd;
+    uint64_t n_pairs;  // n_updates x slots (< 2^31: log_work)
+    uint64_t pair0;    // pairs of the launch's earlier batches
+};
+struct LogsPrepassLaunch {
+    LogsPrepassBatch b[kPrepassBatches];  // 768 bytes
+    uint32_t n_batches;
+    uint64_t n_pairs;            // of all n_batches
+    const unsigned char* pool;
+    uint64_t pool_bytes;
+    uint32_t page_bytes;
+    uint32_t page_shift;
+    uint32_t max_len;
+    uint32_t slots;
+    // the snapshot side (LogCowLaunch's fields); snap_slot null: no cc_cow
+    uint32_t pages_per_chunk;
+    uint32_t words_per_slot;
+    uint32_t n_slots;
+    const uint32_t* snap_slot;
+    unsigned char* snap;
+    uint32_t* snap_crcs;
+    uint32_t* snap_bitmap;
+    const uint32_t* page_crcs;   // the pool's CRC table before the queue
+    unsigned long long* copied;  // += pages copied, or null
+    unsigned long long* stale;   // += copied pages whose bytes mismatch page_crcs (null: no rehash, no LDS image)
+    // the clone side; clone.clone_slot null: no cc_clone (claim is never used)
+    CloneGeo clone;
+    const void* image;
+    uint32_t kconst;
+    int blocks;
+};
+hipError_t launch_logs_prepass(const LogsPrepassLaunch& a, hipStream_t s);
 // cc_clone_check_reads_dev: per read, the touched pages of clone chunks whose bit is clear (one launch)
 struct CloneCheckLaunch {
     CloneGeo geo;

@@ -2970,6 +2970,136 @@ __global__ __launch_bounds__(64 * kCloneWaves) void clone_mark_kernel(CloneMarkL
         });
 }
 
+// cc_apply_logs_cow_dev's pass before the queue: copy2Snapshot and flush()'s
+// bitmap step for EVERY batch of a queue at once.  The pairs (entry, page slot)
+// of the launch's batches form one index space, split evenly and STATICALLY:
+// the space is cut into granules of 16 pairs, a wave step takes four granules a
+// quarter of the space apart (lane l: granule s + S (l / 16), pair l % 16 of
+// it), and the steps go round the workgroups and then round their waves.  So
+// the copies of a skewed queue (all in one batch's first entries) spread over
+// as many waves as there are granules in that stretch, not over the few waves a
+// contiguous share would give them (measured: DESIGN 6a), with no counter and
+// no atomic.  A lane finds its pair's batch with a loop over the descriptors
+// (kernel arguments, read with a wave-uniform index), then its entry and the
+// entry's k-th page.
+//   Snapshot side: a page whose chunk has a slot below n_slots and whose bit
+// is not seen set (a plain read may skip a set bit: bits only rise during the
+// pass) bids with one atomicOr; the lane that gets the word back with the bit
+// clear is the page's only winner among the duplicates (the same page within a
+// batch, across batches, or twice in this step).  It moves the page's stored
+// CRC; the wave then copies the winners' pages as log_cow_kernel does (two in
+// flight, load_page's layout, whole rows, nontemporal stores).  Nothing has
+// written the pool yet, so every copy is the page as it stood before the queue.
+//   Clone side: where the entry covers the page whole and the chunk's clone
+// slot is below n_slots, one atomicOr of its bit unless it is seen set.
+//   Verify rehashes every copied page and counts mismatches (still copied with
+// the stored CRC); without it no LDS image and no CRC arithmetic.  No spin
+// waits; workgroups share the bitmap words and the two counters (one atomicAdd
+// a wave each) and nothing else.
+template <int M, bool Verify>
+__global__ __launch_bounds__(64 * kPrepassWaves) void logs_prepass_kernel(LogsPrepassLaunch a) {
+    __shared__ uint32_t tab[Verify ? kLdsBytes / 4 : 1];
+    constexpr uint32_t pb = 256u * M;  // = a.page_bytes (launch_logs_prepass picks M)
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t S = (((a.n_pairs + 15u) >> 4) + 3u) >> 2;  // wave steps of four granules
+    if (blockIdx.x >= S) return;  // (uniform over the workgroup)
+    if constexpr (Verify) fill_lds<64 * kPrepassWaves>(tab, static_cast<const uint4*>(a.image));
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t c0 = lane << 2 & 0x7Cu;
+    const uint32_t c1 = c0 | 0x10000u;
+    const uint32_t cf = kFinBase + (lane << 2);
+    const bool cow = a.snap_slot != nullptr, clone = a.clone.clone_slot != nullptr;
+    uint32_t ncopied = 0, nstale = 0;
+    // consecutive steps go to different workgroups, then to the next wave of each
+    for (uint64_t s = (uint64_t)wave * gridDim.x + blockIdx.x; s < S; s += (uint64_t)gridDim.x * kPrepassWaves) {
+        const uint64_t pair = ((s + S * (lane >> 4)) << 4) + (lane & 15u);
+        const bool on = pair < a.n_pairs;
+        const uint64_t idx = on ? pair : 0ull;  // (clamped: the loads below need no branch)
+        const UpdateDesc* upd = a.b[0].upd;
+        uint64_t pair0 = 0;
+        for (uint32_t h = 1; h < a.n_batches; h++) {  // the pair's batch: the last one that starts at or before it
+            const uint64_t q0 = a.b[h].pair0;
+            if (idx >= q0) {
+                upd = a.b[h].upd;
+                pair0 = q0;
+            }
+        }
+        const uint32_t t = (uint32_t)(idx - pair0);  // < the batch's n_pairs < 2^31
+        const uint32_t i = t / a.slots, k = t - i * a.slots;
+        const UpdateDesc d = upd[i];
+        // the write log's rule, as insert_piece applies it: an entry that breaks it has no pair
+        const bool ok = on && d.len >= 1 && d.len <= a.max_len && d.dst < a.pool_bytes && d.len <= a.pool_bytes - d.dst;
+        const uint64_t pg0 = ok ? d.dst >> a.page_shift : 0;
+        const uint64_t pg1 = ok ? (d.dst + d.len - 1) >> a.page_shift : 0;
+        const bool pok = ok && pg0 + k <= pg1;
+        const uint32_t key = pok ? (uint32_t)(pg0 + k) : 0u;  // the page (< 2^32 - 1 pool pages)
+        bool win = false;
+        uint64_t sidx = 0;  // page of d_snap / entry of d_snap_crcs
+        uint32_t oc = 0;
+        if (cow) {
+            const uint32_t chunk = key / a.pages_per_chunk;
+            const uint32_t q = key - chunk * a.pages_per_chunk;  // the page within its chunk
+            const uint32_t slot = pok ? a.snap_slot[chunk] : 0xFFFFFFFFu;
+            const bool has = pok && slot < a.n_slots;  // CC_NO_SNAPSHOT and any slot out of range: written in place
+            uint32_t* word = a.snap_bitmap + ((uint64_t)(has ? slot : 0u) * a.words_per_slot + (q >> 5));
+            const uint32_t bit = 1u << (q & 31u);
+            if (has && !(*word & bit)) win = !(atomicOr(word, bit) & bit);  // a set bit: the snapshot keeps its first version
+            if (win) {
+                sidx = (uint64_t)slot * a.pages_per_chunk + q;
+                oc = a.page_crcs[key];
+                a.snap_crcs[sidx] = oc;  // moved, not recomputed
+            }
+        }
+        if (clone && pok && ((uint64_t)key << a.page_shift) >= d.dst &&
+            ((uint64_t)key + 1u) << a.page_shift <= d.dst + d.len) {  // covered whole (cc_clone_mark_dev's rule)
+            const uint64_t c = clone_chunk_of(a.clone, key);
+            const uint32_t q = (uint32_t)(key - c * a.clone.pages_per_chunk);
+            const uint32_t s = a.clone.clone_slot[c];
+            if (s < a.clone.n_slots) {
+                uint32_t* word = a.clone.bitmap + (uint64_t)s * a.clone.words_per_slot + (q >> 5);
+                const uint32_t bit = 1u << (q & 31u);
+                if (!(*word & bit)) atomicOr(word, bit);
+            }
+        }
+        uint64_t todo = __ballot(win);
+        ncopied += (uint32_t)__popcll(todo);
+        while (todo) {
+            // two pages in flight: both loads, then both stores
+            const uint32_t b0 = (uint32_t)__builtin_ctzll(todo);
+            todo &= todo - 1ull;
+            const bool two = todo != 0ull;
+            const uint32_t b1 = two ? (uint32_t)__builtin_ctzll(todo) : b0;
+            todo &= todo - 1ull;  // (0 stays 0)
+            const uint32_t p0 = __builtin_amdgcn_readlane(key, b0), p1 = __builtin_amdgcn_readlane(key, b1);
+            const uint64_t d0 = readlane64(sidx, b0), d1 = readlane64(sidx, b1);
+            uint32_t w0[M], w1[M];
+            load_page<M>(w0, reinterpret_cast<const uint32_t*>(a.pool + (uint64_t)p0 * pb) + lane);
+            load_page<M>(w1, reinterpret_cast<const uint32_t*>(a.pool + (uint64_t)p1 * pb) + lane);
+            uint32_t* o0 = reinterpret_cast<uint32_t*>(a.snap + d0 * pb) + lane;
+            uint32_t* o1 = reinterpret_cast<uint32_t*>(a.snap + d1 * pb) + lane;
+#pragma unroll
+            for (int j = 0; j < M; j++) __builtin_nontemporal_store(w0[j], o0 + 64 * j);
+            if (two) {
+#pragma unroll
+                for (int j = 0; j < M; j++) __builtin_nontemporal_store(w1[j], o1 + 64 * j);
+            }
+            if constexpr (Verify) {
+                const uint32_t e0 = __builtin_amdgcn_readlane(oc, b0), e1 = __builtin_amdgcn_readlane(oc, b1);
+                const uint32_t r0 = wave_xor(apply_fin(tab, chain<M>(tab, w0, c0, c1), cf)) ^ a.kconst;
+                nstale += r0 != e0 ? 1u : 0u;
+                if (two) {
+                    const uint32_t r1 = wave_xor(apply_fin(tab, chain<M>(tab, w1, c0, c1), cf)) ^ a.kconst;
+                    nstale += r1 != e1 ? 1u : 0u;
+                }
+            }
+        }
+    }
+    if (lane == 0) {
+        if (a.copied && ncopied) atomicAdd(a.copied, (unsigned long long)ncopied);
+        if (Verify && nstale) atomicAdd(a.stale, (unsigned long long)nstale);
+    }
+}
+
 // cc_clone_check_reads_dev: Read's NextClearBit test for a batch.  Every page a
 // read touches that lies in a clone chunk with a clear bit counts on its read;
 // a read past the pool is marked by the lane that loads it.
@@ -4009,6 +4139,32 @@ hipError_t launch_paste(const PasteLaunch& a, hipStream_t s) {
 hipError_t launch_clone_mark(const CloneMarkLaunch& a, hipStream_t s) {
     if (a.n == 0 || a.geo.n_slots == 0) return hipSuccess;
     hipLaunchKernelGGL(clone_mark_kernel, clone_grid(a.n, a.blocks), dim3(64 * kCloneWaves), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_logs_prepass(const LogsPrepassLaunch& a, hipStream_t s) {
+    if (a.n_batches == 0 || a.n_batches > (uint32_t)kPrepassBatches || a.n_pairs == 0 || a.slots == 0 || a.blocks <= 0)
+        return hipErrorInvalidValue;
+    if (a.page_bytes != 1u << a.page_shift || (a.snap_slot && a.pages_per_chunk == 0) ||
+        (a.clone.clone_slot && a.clone.pages_per_chunk == 0))
+        return hipErrorInvalidValue;
+#define CC_PPCASE(MM)                                                                                                \
+    case MM:                                                                                                         \
+        if (a.stale)                                                                                                 \
+            hipLaunchKernelGGL((logs_prepass_kernel<MM, true>), dim3(a.blocks), dim3(64 * kPrepassWaves), 0, s, a);  \
+        else                                                                                                         \
+            hipLaunchKernelGGL((logs_prepass_kernel<MM, false>), dim3(a.blocks), dim3(64 * kPrepassWaves), 0, s, a); \
+        break;
+    switch (a.page_bytes / kWaveBytes) {
+        CC_PPCASE(1)
+        CC_PPCASE(2)
+        CC_PPCASE(4)
+        CC_PPCASE(8)
+        CC_PPCASE(16)
+        CC_PPCASE(32)
+        default: return hipErrorInvalidValue;
+    }
+#undef CC_PPCASE
     return hipGetLastError();
 }
 

@@ -328,9 +328,10 @@ int cc_apply_log_delta_dev(void* d_pool, uint64_t pool_bytes, uint32_t page_byte
  * page_bytes that divides pool_bytes; every pointer but the two counters
  * non-NULL; d_snap 4-byte aligned.
  *
- * Not covered: the queue (cc_apply_logs_dev groups batch k+1 in batch k's page
- * kernel, which leaves no boundary for the pass: take one call per batch while
- * a snapshot is open); clone chunks and Paste.  (Reading a snapshot back:
+ * Not covered by this call: a queue of batches (that is cc_apply_logs_cow_dev:
+ * one pass before the whole queue, then cc_apply_logs_dev's launches, so a
+ * pool with open snapshots keeps the pipelined queue); clone chunks and Paste
+ * (cc_paste_dev, cc_clone_mark_dev).  (Reading a snapshot back:
  * cc_read_snap_dev.) */
 #define CC_NO_SNAPSHOT 0xFFFFFFFFu
 typedef struct cc_cow {
@@ -550,6 +551,60 @@ int cc_paste_dev(void* d_pool, uint64_t pool_bytes, uint32_t page_bytes, const v
  * caller sees that in the bitmap it reads back for the metapage. */
 int cc_clone_mark_dev(uint64_t pool_bytes, uint32_t page_bytes, const cc_update* d_log, uint64_t n_updates,
                       uint32_t max_len, const cc_clone* clone, void* stream);
+
+/* The QUEUE of write logs (cc_apply_logs_dev) for a pool with open snapshots
+ * and/or clone chunks: the pipelined queue, with the copy-on-write pass and the
+ * clone marks of ALL its batches done in one pass before its first write.
+ *
+ * Equivalence: for every non-empty batch k in order, take
+ * cc_apply_log_cow_dev(batch k, delta, cow) followed, when clone != NULL, by
+ * cc_clone_mark_dev(batch k's log, max_len, clone), all on `stream`.  This call
+ * leaves the pool, d_page_crcs, d_snap (copied pages only; every other slot
+ * byte untouched), d_snap_crcs, d_snap_bitmap, *d_copied, *d_stale and the
+ * clone d_bitmap bit for bit as that sequence leaves them.  Why one pass up
+ * front is enough: d_snap_slot is read once per call; a snapshot keeps a page's
+ * FIRST version; and the first batch of the queue that touches page p finds p
+ * and d_page_crcs[p] exactly as they stood before the queue.  The clone marks
+ * are idempotent ORs that no log kernel reads.  d_claim is not touched.
+ * Nothing is written outside d_snap for a slot >= n_slots, or behind d_bitmap
+ * for a CC_NOT_CLONE chunk.
+ *
+ * cow == NULL && clone == NULL IS cc_apply_logs_dev: same code path, same
+ * launches.  Either struct alone is allowed.  A chunk that carries both a
+ * snapshot slot and a clone slot is a caller error in the reference; here each
+ * struct is applied on its own terms and nothing is undefined.
+ *
+ * Per entry the write log's rule holds: 1 <= len <= max_len, dst < pool_bytes,
+ * len <= pool_bytes - dst; an entry that breaks it copies nothing, marks
+ * nothing and writes nothing.  A page is copied when a valid entry touches it
+ * (cc_apply_log_cow_dev's rule); a clone bit is set only for a page that one
+ * entry covers WHOLE (cc_clone_mark_dev's rule: a partly covered page keeps its
+ * bit, and two partial entries that together cover a page do not count).
+ * d_stale, when non-NULL, makes the pass rehash every page it copies, as in
+ * cc_apply_log_cow_dev.  In full mode too d_page_crcs must hold the CRCs of
+ * the pages before the queue.
+ *
+ * d_work / work_bytes: as for cc_apply_logs_dev (cc_apply_logs_work_bytes);
+ * the pass needs no caller memory, makes no host-to-device copy and allocates
+ * nothing: the batch descriptors ride in the kernel argument, 32 a launch.
+ *
+ * Checked before a device is needed (CC_EINVAL): cc_apply_logs_dev's checks;
+ * cc_apply_log_cow_dev's checks on cow; cc_clone_mark_dev's checks on clone,
+ * every batch's n_updates < 2^31 among them.  A malformed cow or clone is
+ * refused even for an empty queue.  n_batches == 0, or only empty batches:
+ * CC_OK.  No GPU: CC_ENODEV, never a CPU fallback.
+ *
+ * Launches: ceil(non-empty batches / 32) for the pass, then exactly those of
+ * cc_apply_logs_dev: batches of <= 64 entries no longer than a page keep the
+ * one-launch path, and a stream without an engine table takes the pass and
+ * then one plain cc_apply_log*_dev per batch.  needCow is decided per chunk per
+ * CALL, as in cc_apply_log_cow_dev: the caller splits a queue at the request
+ * that creates a snapshot.  The caller must not run another call over the same
+ * slots or bitmaps on another stream at the same time.  Not covered: Paste
+ * inside the queue. */
+int cc_apply_logs_cow_dev(void* d_pool, uint64_t pool_bytes, uint32_t page_bytes, const cc_log_batch* batches,
+                          uint32_t n_batches, uint32_t max_len, uint32_t* d_page_crcs, int delta, void* d_work,
+                          uint64_t work_bytes, void* stream, const cc_cow* cow, const cc_clone* clone);
 
 /* The NextClearBit test of CSChunkFile::Read on a clone chunk
  * (chunkserver_chunkfile.cpp:510-526: a range with any clear bit is refused
