@@ -104,6 +104,15 @@ class CcClone(ctypes.Structure):
 
 
 CC_NOT_CLONE = 0xFFFFFFFF
+
+
+class CcOpBatch(ctypes.Structure):
+    """cc_op_batch (include/curve_crc.h): one batch of a cc_apply_ops_dev queue, a write log or a paste batch."""
+    _fields_ = [("kind", _u32), ("reserved", _u32), ("d_src", _vp), ("src_bytes", _u64), ("d_recs", _vp), ("n", _u64),
+                ("d_pasted_per_entry", _vp)]
+
+
+CC_OP_WRITE, CC_OP_PASTE = 0, 1
 CC_NO_ORIGIN = 0xFFFFFFFFFFFFFFFF  # cc_read_merge_dev: d_origin_off[i] of a read with no origin
 
 
@@ -164,6 +173,8 @@ SIGNATURES = {
     "cc_apply_logs_dev": (_int, [_vp, _u64, _u32, _vp, _u32, _u32, _vp, _int, _vp, _u64, _vp]),
     "cc_apply_logs_cow_dev": (_int, [_vp, _u64, _u32, _vp, _u32, _u32, _vp, _int, _vp, _u64, _vp,
                                      ctypes.POINTER(CcCow), ctypes.POINTER(CcClone)]),
+    "cc_apply_ops_dev": (_int, [_vp, _u64, _u32, _vp, _u32, _u32, _u32, _vp, _int, _vp, _u64, _vp,
+                                ctypes.POINTER(CcCow), ctypes.POINTER(CcClone), _vp]),
     "cc_verify_reads_work_bytes": (_u64, [_u64]),
     "cc_verify_reads_dev": (_int, [_vp, _u64, _u32, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _vp]),
     "cc_read_snap_dev": (_int, [_vp, _u64, _u32, _vp, _u64, _vp, ctypes.POINTER(CcCow), _vp, _vp, _u64, _vp, _vp,

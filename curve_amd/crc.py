@@ -959,6 +959,82 @@ def clone_mark(pool, d_log, n_updates: int, max_len: int, clone: Clone, page_byt
         _record_clone(clone, stream)
 
 
+def apply_ops(pool, page_crcs, ops, max_len: int, max_paste_len: int, page_bytes: int = PAGE_SIZE, stream=None,
+              delta: bool = False, cow: Optional["Cow"] = None, clone: Optional[Clone] = None, contested=None):
+    """cc_apply_ops_dev: a queue of write logs AND paste batches, in log order,
+    as one call -- a chunkserver's apply loop.  `ops`: a list of
+    ("write", src, d_log, n) and ("paste", origin, d_pastes, n) items (device
+    tensors; d_log / d_pastes hold cc_update records, log_records).  Every page
+    whose first setter in the queue is a paste entry is pasted before the
+    queue's first write; then the write batches run as apply_logs(cow=, clone=)
+    runs them.  The result equals apply_log_cow + clone_mark / paste per batch
+    bit for bit unless an unaligned write precedes a paste of the same page;
+    such pairs are ADDED to `contested` (int64 [1] device tensor, optional).
+    Returns the per-paste-batch count tensors (int32 [n], -1 = invalid entry),
+    in queue order.  Without a paste item this is apply_logs.  No host sync."""
+    import ctypes
+    torch = _torch()
+    kinds = {"write": _lib.CC_OP_WRITE, "paste": _lib.CC_OP_PASTE}
+    for item in ops:
+        if item[0] not in kinds:
+            raise CurveCrcError(_lib.CC_EINVAL, f"unknown op kind {item[0]!r}")
+    if not any(kind == "paste" for kind, _, _, _ in ops):
+        apply_logs(pool, page_crcs, [(src, d_log, n) for _, src, d_log, n in ops], max_len, page_bytes, stream=stream,
+                   delta=delta, cow=cow, clone=clone)
+        return []
+    n_max = max([int(n) for kind, _, _, n in ops if kind == "write"] + [1])
+    need = int(lib().cc_apply_logs_work_bytes(n_max, max(max_len, 1), page_bytes))
+    if need == 0:
+        raise CurveCrcError(_lib.CC_EINVAL, "unsupported log geometry")
+    key = ("logs",) + tuple(_stream_key(pool.device, stream))
+    work = _log_work.get(key)
+    if work is None or work.numel() < need:
+        with _on_stream(stream):
+            work = torch.empty(need, dtype=torch.uint8, device=pool.device)
+        _log_work[key] = work
+    arr = (_lib.CcOpBatch * len(ops))()
+    counts = []
+    for i, (kind, src, d_recs, n) in enumerate(ops):
+        arr[i].kind = kinds[kind]
+        arr[i].n = int(n)
+        if not int(n) and kind == "write":
+            continue
+        if int(n):
+            arr[i].d_src = _dev_ptr(src, "src").value
+            arr[i].d_recs = _dev_ptr(d_recs, "records").value
+        if kind == "paste":
+            with _on_stream(stream):
+                per = torch.zeros(max(int(n), 1), dtype=torch.int32, device=pool.device)
+            counts.append(per[:int(n)])
+            if int(n):
+                arr[i].src_bytes = _nbytes(src)
+                arr[i].d_pasted_per_entry = _dev_ptr(per, "pasted_per_entry").value
+    ws = cow.struct() if cow is not None else None
+    ls = clone.struct() if clone is not None else None
+    with torch.cuda.device(pool.device):
+        check(lib().cc_apply_ops_dev(_dev_ptr(pool, "pool"), _nbytes(pool), page_bytes, ctypes.cast(arr, ctypes.c_void_p),
+                                     len(ops), max_len, max_paste_len, _dev_ptr(page_crcs, "page_crcs"),
+                                     1 if delta else 0, _dev_ptr(work, "work"), work.numel(), _stream_handle(stream),
+                                     ctypes.byref(ws) if ws is not None else None,
+                                     ctypes.byref(ls) if ls is not None else None,
+                                     _dev_ptr(contested, "contested") if contested is not None else None),
+              "cc_apply_ops_dev")
+    if stream is not None:
+        work.record_stream(stream)
+        for t in counts:
+            t.record_stream(stream)
+        if contested is not None:
+            contested.record_stream(stream)
+        if cow is not None:
+            _record_cow(cow, stream)
+            for t in (cow.copied, cow.stale):
+                if t is not None:
+                    t.record_stream(stream)
+        if clone is not None:
+            _record_clone(clone, stream)
+    return counts
+
+
 def clone_check_reads(pool, offsets, lengths, clone: Clone, page_bytes: int = PAGE_SIZE, stream=None):
     """cc_clone_check_reads_dev: for the reads (offsets, lengths; any
     alignment) of the pool, how many of the pages each touches lie in a clone

@@ -1727,9 +1727,12 @@ hipError_t logs_prepass(DevCtx* c, hipStream_t s, const unsigned char* d_pool, u
     return a.n_batches ? flush() : hipSuccess;
 }
 
-int apply_logs(void* d_pool, uint64_t pool_bytes, uint32_t page_bytes, const cc_log_batch* batches, uint32_t n_batches,
-               uint32_t max_len, uint32_t* d_page_crcs, int delta, void* d_work, uint64_t work_bytes, void* stream,
-               const cc_cow* cow, const cc_clone* clone) {
+// The queue's argument checks, before a device is needed (cc_apply_ops_dev runs
+// them before its own launches).  CC_OK with *max_n == 0: nothing to apply.
+int logs_check(const void* d_pool, uint64_t pool_bytes, uint32_t page_bytes, const cc_log_batch* batches,
+               uint32_t n_batches, uint32_t max_len, const uint32_t* d_page_crcs, const void* d_work, uint64_t work_bytes,
+               const cc_cow* cow, const cc_clone* clone, LogsWork* W, uint64_t* max_n_out) {
+    *max_n_out = 0;
     if (!log_page_ok(page_bytes)) return CC_EINVAL;
     if (cow) {  // apply_log's checks: a malformed struct is refused even for an empty queue
         if (cow->chunk_bytes == 0 || cow->chunk_bytes % page_bytes || pool_bytes % cow->chunk_bytes) return CC_EINVAL;
@@ -1749,10 +1752,21 @@ int apply_logs(void* d_pool, uint64_t pool_bytes, uint32_t page_bytes, const cc_
         max_n = b.n_updates > max_n ? b.n_updates : max_n;
     }
     if (max_n == 0) return CC_OK;
+    if (!logs_work(max_n, max_len, page_bytes, W) || work_bytes < W->bytes) return CC_EINVAL;
+    *max_n_out = max_n;
+    return CC_OK;
+}
+
+int apply_logs(void* d_pool, uint64_t pool_bytes, uint32_t page_bytes, const cc_log_batch* batches, uint32_t n_batches,
+               uint32_t max_len, uint32_t* d_page_crcs, int delta, void* d_work, uint64_t work_bytes, void* stream,
+               const cc_cow* cow, const cc_clone* clone) {
     LogsWork W;
-    if (!logs_work(max_n, max_len, page_bytes, &W) || work_bytes < W.bytes) return CC_EINVAL;
+    uint64_t max_n;
+    int rc = logs_check(d_pool, pool_bytes, page_bytes, batches, n_batches, max_len, d_page_crcs, d_work, work_bytes, cow,
+                        clone, &W, &max_n);
+    if (rc || max_n == 0) return rc;
     CtxRef c;
-    int rc = get_ctx(&c);
+    rc = get_ctx(&c);
     if (rc) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const uint32_t slots = log_slots(max_len, page_bytes);
@@ -2185,6 +2199,105 @@ int cc_clone_mark_dev(uint64_t pool_bytes, uint32_t page_bytes, const cc_update*
     a.n = n_updates;
     a.blocks = c->cus;
     return map_err(launch_clone_mark(a, static_cast<hipStream_t>(stream)));
+}
+
+// ---- write logs and paste batches in one queue (cc_apply_ops_dev) ----
+int cc_apply_ops_dev(void* d_pool, uint64_t pool_bytes, uint32_t page_bytes, const cc_op_batch* ops, uint32_t n_ops,
+                     uint32_t max_len, uint32_t max_paste_len, uint32_t* d_page_crcs, int delta, void* d_work,
+                     uint64_t work_bytes, void* stream, const cc_cow* cow, const cc_clone* clone, uint64_t* d_contested) {
+    static_assert(sizeof(cc_op_batch) == 48, "cc_op_batch: six 8-byte fields");
+    static_assert(CC_OP_WRITE == kOpWrite && CC_OP_PASTE == kOpPaste, "the kernels' kinds are the header's");
+    if (!log_page_ok(page_bytes)) return CC_EINVAL;
+    if (n_ops && !ops) return CC_EINVAL;
+    // the write batches, as cc_apply_logs_cow_dev takes them; the paste batches' own checks
+    std::vector<cc_log_batch> writes;
+    uint64_t total = 0;
+    int64_t last_paste = -1;  // the last non-empty paste batch
+    for (uint32_t k = 0; k < n_ops; k++) {
+        const cc_op_batch& o = ops[k];
+        if ((o.kind != CC_OP_WRITE && o.kind != CC_OP_PASTE) || o.reserved != 0) return CC_EINVAL;
+        total += o.n;
+        if (total >= (1ull << 31) - 1) return CC_EINVAL;  // ordinals live in d_claim: 2 x ordinal + kind below all-ones
+        if (o.kind == CC_OP_WRITE) {
+            writes.push_back(cc_log_batch{o.d_src, o.d_recs, o.n});
+        } else if (o.n) {  // cc_paste_dev's checks
+            if (!o.d_src || !o.d_recs || !o.d_pasted_per_entry || ((uintptr_t)o.d_src & 3u)) return CC_EINVAL;
+            last_paste = k;
+        }
+    }
+    LogsWork W;
+    uint64_t max_n;
+    int rc = logs_check(d_pool, pool_bytes, page_bytes, writes.data(), (uint32_t)writes.size(), max_len, d_page_crcs, d_work,
+                        work_bytes, cow, clone, &W, &max_n);
+    if (rc) return rc;
+    if (last_paste < 0)  // no paste to place: this IS cc_apply_logs_cow_dev
+        return apply_logs(d_pool, pool_bytes, page_bytes, writes.data(), (uint32_t)writes.size(), max_len, d_page_crcs, delta,
+                          d_work, work_bytes, stream, cow, clone);
+    if (!d_pool || !d_page_crcs || pool_bytes % page_bytes || ((uintptr_t)d_pool & 3u)) return CC_EINVAL;
+    if (!clone_ok(clone, pool_bytes, page_bytes)) return CC_EINVAL;
+    if (max_paste_len == 0 || max_paste_len % page_bytes) return CC_EINVAL;
+    const uint32_t paste_slots = max_paste_len / page_bytes;
+    for (uint32_t k = 0; k < n_ops; k++)  // a batch's pairs are indexed in 32 bits
+        if (ops[k].kind == CC_OP_PASTE && ops[k].n * paste_slots >= (1ull << 32)) return CC_EINVAL;
+    CtxRef c;
+    rc = get_ctx(&c);
+    if (rc) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    OpsLaunch a = {};
+    a.pool = static_cast<uint32_t*>(d_pool);
+    a.pool_bytes = pool_bytes;
+    a.page_bytes = page_bytes;
+    a.page_shift = (uint32_t)__builtin_ctz(page_bytes);  // a power of two (log_page_ok)
+    a.max_len = max_len ? max_len : 1;  // (0 only without write entries: logs_check)
+    a.max_paste_len = max_paste_len;
+    a.slots = log_slots(a.max_len, page_bytes);
+    a.paste_slots = paste_slots;
+    a.page_crcs = d_page_crcs;
+    a.geo = clone_geo(clone, page_bytes);
+    a.pasted = reinterpret_cast<unsigned long long*>(clone->d_pasted);
+    a.contested = reinterpret_cast<unsigned long long*>(d_contested);
+    a.image = c->image;
+    a.kconst = kconst_for(page_bytes);
+    // One pass kind over the non-empty batches 0 .. last_paste that `take` selects, kOpsBatches descriptors a launch.
+    // per_cu: workgroups a CU (the PASTE kernel's LDS image fills the CU).
+    auto pass = [&](hipError_t (*launch)(const OpsLaunch&, hipStream_t), uint32_t per_cu, auto take) {
+        auto flush = [&]() {
+            const uint64_t wb = (a.n_pairs + 64u * kOpsWaves - 1) / (64u * kOpsWaves);
+            const uint64_t cap = (uint64_t)c->cus * per_cu;
+            a.blocks = (int)(wb < cap ? wb : cap);
+            const hipError_t e = launch(a, s);
+            a.n_batches = 0;
+            a.n_pairs = 0;
+            return e;
+        };
+        uint64_t ord = 0;
+        for (uint32_t k = 0; k <= (uint32_t)last_paste; ord += ops[k].n, k++) {
+            const cc_op_batch& o = ops[k];
+            if (o.n == 0 || !take(o.kind)) continue;
+            OpsBatch& b = a.b[a.n_batches++];
+            b.recs = reinterpret_cast<const UpdateDesc*>(o.d_recs);
+            b.src = static_cast<const unsigned char*>(o.d_src);
+            b.src_bytes = o.src_bytes;
+            b.pasted_per_entry = o.d_pasted_per_entry;
+            b.pair0 = a.n_pairs;
+            b.ord0 = (uint32_t)ord;
+            b.kind = o.kind;
+            a.n_pairs += o.n * (o.kind == CC_OP_PASTE ? a.paste_slots : a.slots);
+            if (a.n_batches == (uint32_t)kOpsBatches) {
+                const hipError_t e = flush();
+                if (e != hipSuccess) return e;
+            }
+        }
+        return a.n_batches ? flush() : hipSuccess;
+    };
+    hipError_t e = pass(launch_ops_bid, 2, [](uint32_t) { return true; });
+    // with no bitmaps nothing bids: BID has marked the invalid entries, and nothing can be pasted
+    if (e == hipSuccess && a.geo.n_slots) e = pass(launch_ops_resolve, 2, [](uint32_t kind) { return kind == CC_OP_WRITE; });
+    if (e == hipSuccess && a.geo.n_slots) e = pass(launch_ops_paste, 1, [](uint32_t kind) { return kind == CC_OP_PASTE; });
+    if (e != hipSuccess) return map_err(e);
+    // the queue's own launches over the write batches, exactly cc_apply_logs_cow_dev's
+    return apply_logs(d_pool, pool_bytes, page_bytes, writes.data(), (uint32_t)writes.size(), max_len, d_page_crcs, delta,
+                      d_work, work_bytes, stream, cow, clone);
 }
 
 int cc_clone_check_reads_dev(uint64_t pool_bytes, uint32_t page_bytes, const cc_range* d_reads, uint64_t n_reads,

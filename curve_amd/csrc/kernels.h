@@ -391,6 +391,53 @@ struct LogsPrepassLaunch {
     int blocks;
 };
 hipError_t launch_logs_prepass(const LogsPrepassLaunch& a, hipStream_t s);
+// cc_apply_ops_dev: a queue of write logs AND paste batches.  Three pass kinds
+// run before the queue's own launches, each over (entry, page slot) pairs with
+// a lane per pair, the batch descriptors in the kernel argument as above:
+//   BID      batches 0 .. the last paste batch: a paste pair, and a write pair
+//            that covers its page whole, bids for a clone page whose bit is clear
+//            with atomicMin(claim, 2 x ordinal + kind); marks invalid paste entries
+//   RESOLVE  the write batches among them: a pair that finds its own key puts
+//            all-ones back; a pair covering its page partly that finds the key of
+//            a LATER paste counts one contested pair
+//   PASTE    the paste batches: the pair that finds its own key copies and hashes
+//            its source page, writes the CRC, sets the bit, counts and resets
+// An entry's ordinal is its position in the queue (ord0 of its batch + its index).
+constexpr int kOpsBatches = 32;
+constexpr int kOpsWaves = 16;  // waves per workgroup of the three kernels
+constexpr uint32_t kOpWrite = 0, kOpPaste = 1;  // CC_OP_WRITE, CC_OP_PASTE
+struct OpsBatch {
+    const UpdateDesc* recs;
+    const unsigned char* src;    // paste: the batch's origin buffer
+    uint64_t src_bytes;          // paste: its size
+    uint32_t* pasted_per_entry;  // paste: [n] += pages entry i pasted; UINT32_MAX for an invalid entry
+    uint64_t pair0;              // pairs of the launch's earlier batches
+    uint32_t ord0;               // ordinal of the batch's entry 0
+    uint32_t kind;               // kOpWrite | kOpPaste
+};
+struct OpsLaunch {
+    OpsBatch b[kOpsBatches];     // 1536 bytes
+    uint32_t n_batches;
+    uint64_t n_pairs;            // of all n_batches
+    uint32_t* pool;
+    uint64_t pool_bytes;
+    uint32_t page_bytes;
+    uint32_t page_shift;
+    uint32_t max_len;            // write entries: the write log's rule
+    uint32_t max_paste_len;      // paste entries: a multiple of page_bytes
+    uint32_t slots;              // pairs a write entry (log_slots)
+    uint32_t paste_slots;        // pairs a paste entry: max_paste_len / page_bytes
+    uint32_t* page_crcs;
+    CloneGeo geo;
+    unsigned long long* pasted;     // += pages pasted, or null
+    unsigned long long* contested;  // += contested (write entry, page) pairs, or null
+    const void* image;
+    uint32_t kconst;
+    int blocks;
+};
+hipError_t launch_ops_bid(const OpsLaunch& a, hipStream_t s);
+hipError_t launch_ops_resolve(const OpsLaunch& a, hipStream_t s);
+hipError_t launch_ops_paste(const OpsLaunch& a, hipStream_t s);
 // cc_clone_check_reads_dev: per read, the touched pages of clone chunks whose bit is clear (one launch)
 struct CloneCheckLaunch {
     CloneGeo geo;

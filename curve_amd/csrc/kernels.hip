@@ -3100,6 +3100,231 @@ __global__ __launch_bounds__(64 * kPrepassWaves) void logs_prepass_kernel(LogsPr
     }
 }
 
+// ---------------------------------------------------------------------------
+// cc_apply_ops_dev: paste batches inside the write-log queue.  Three pass kinds
+// before the queue's own launches (BID, RESOLVE, PASTE: kernels.h), each a lane
+// per (entry, page slot) pair on logs_prepass_kernel's static split: granules
+// of 16 pairs, four a wave step a quarter of the space apart, steps round the
+// workgroups and then round their waves.  A page's FIRST SETTER -- the entry of
+// the lowest ordinal that is a valid paste covering it or a valid write covering
+// it whole -- is found with atomicMin on the page's claim word; the key
+// 2 x ordinal + kind orders by ordinal and tells a paste (odd) from a write
+// (even).  All-ones (odd, but no key: ordinals stay below 2^31 - 1) is "no bid".
+// ---------------------------------------------------------------------------
+// The pair a lane holds in wave step s of S: its batch's descriptor (found with
+// a loop over the kernel argument, wave-uniform index), its entry's record and
+// ordinal, and the page slot k within the entry.
+struct OpsPair {
+    bool on;             // a pair of the launch (the rest is pair 0's when not)
+    UpdateDesc d;
+    uint32_t h;          // descriptor index
+    uint32_t i, k;       // entry of the batch, page slot of the entry
+    uint32_t ord, kind;  // the entry's ordinal; the batch's kind
+    uint64_t src_bytes;  // the batch's (paste)
+};
+__device__ __forceinline__ OpsPair ops_pair_of(const OpsLaunch& a, uint64_t s, uint64_t S, uint32_t lane) {
+    OpsPair p;
+    const uint64_t pair = ((s + S * (lane >> 4)) << 4) + (lane & 15u);
+    p.on = pair < a.n_pairs;
+    const uint64_t idx = p.on ? pair : 0ull;  // (clamped: the loads below need no branch)
+    const UpdateDesc* recs = a.b[0].recs;
+    uint64_t pair0 = 0;
+    p.h = 0;
+    p.ord = a.b[0].ord0;
+    p.kind = a.b[0].kind;
+    p.src_bytes = a.b[0].src_bytes;
+    for (uint32_t h = 1; h < a.n_batches; h++) {  // the pair's batch: the last one that starts at or before it
+        const uint64_t q0 = a.b[h].pair0;
+        if (idx >= q0) {
+            recs = a.b[h].recs;
+            pair0 = q0;
+            p.h = h;
+            p.ord = a.b[h].ord0;
+            p.kind = a.b[h].kind;
+            p.src_bytes = a.b[h].src_bytes;
+        }
+    }
+    const uint32_t t = (uint32_t)(idx - pair0);  // < the batch's pairs < 2^32 (checked by the host)
+    const uint32_t per = p.kind == kOpPaste ? a.paste_slots : a.slots;
+    p.i = t / per;
+    p.k = t - p.i * per;
+    p.ord += p.i;
+    p.d = recs[p.i];
+    return p;
+}
+// the write log's rule, as insert_piece applies it
+__device__ __forceinline__ bool ops_write_ok(const OpsLaunch& a, const UpdateDesc& d) {
+    return d.len >= 1 && d.len <= a.max_len && d.dst < a.pool_bytes && d.len <= a.pool_bytes - d.dst;
+}
+// cc_paste_dev's rule (paste_bad) and len <= max_paste_len, which bounds an entry's pairs (len == 0 is valid)
+__device__ __forceinline__ bool ops_paste_bad(const OpsLaunch& a, const UpdateDesc& u, uint64_t src_bytes) {
+    if (!u.len) return false;
+    if ((u.dst | u.len) & (uint64_t)(a.page_bytes - 1u)) return true;
+    if (u.len > a.max_paste_len) return true;
+    if (u.dst >= a.pool_bytes || u.len > a.pool_bytes - u.dst) return true;
+    return (u.src & 3u) || u.src > src_bytes || u.len > src_bytes - u.src;
+}
+// A page of the pool behind the clone tables: its claim word's index, or false
+// for a page of a chunk that is no clone.  `page` lies inside the pool.
+__device__ __forceinline__ bool ops_claim_of(const CloneGeo& g, uint64_t page, uint32_t& s, uint32_t& q, uint64_t& cidx) {
+    const uint64_t c = clone_chunk_of(g, page);
+    q = (uint32_t)(page - c * g.pages_per_chunk);
+    s = g.clone_slot[c];
+    if (s >= g.n_slots) return false;
+    cidx = (uint64_t)s * g.pages_per_chunk + q;
+    return true;
+}
+
+// BID: no page traffic.  A valid paste pair, and a valid write pair that covers
+// its page whole, bids with its key where the page's chunk is a clone and its
+// bit is clear; the lowest key holds the claim word when every BID launch of
+// the call has ended.  The lane with page slot 0 of an invalid paste entry
+// marks it.  Reads the bitmap and writes none (the bits rise in PASTE and in the
+// queue's own pass, both later on the stream).
+__global__ __launch_bounds__(64 * kOpsWaves) void ops_bid_kernel(OpsLaunch a) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t S = (((a.n_pairs + 15u) >> 4) + 3u) >> 2;  // wave steps of four granules
+    if (blockIdx.x >= S) return;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    for (uint64_t s = (uint64_t)wave * gridDim.x + blockIdx.x; s < S; s += (uint64_t)gridDim.x * kOpsWaves) {
+        const OpsPair p = ops_pair_of(a, s, S, lane);
+        const bool paste = p.kind == kOpPaste;
+        const bool bad = p.on && paste && ops_paste_bad(a, p.d, p.src_bytes);
+        uint64_t mark = __ballot(bad && p.k == 0);
+        while (mark) {  // (rare) the entry's word lies behind its batch's pointer: a uniform descriptor index
+            const uint32_t b = (uint32_t)__builtin_ctzll(mark);
+            mark &= mark - 1ull;
+            uint32_t* per = a.b[__builtin_amdgcn_readlane(p.h, b)].pasted_per_entry;
+            if (lane == b) per[p.i] = 0xFFFFFFFFu;
+        }
+        const uint64_t page = (p.d.dst >> a.page_shift) + p.k;
+        bool bid;
+        if (paste)
+            bid = p.on && !bad && p.k < (p.d.len >> a.page_shift);
+        else  // covered whole (cc_clone_mark_dev's rule); dst + len <= pool_bytes: no overflow
+            bid = p.on && ops_write_ok(a, p.d) && (page << a.page_shift) >= p.d.dst &&
+                  ((page + 1u) << a.page_shift) <= p.d.dst + p.d.len;
+        if (!bid) continue;
+        uint32_t sl, q;
+        uint64_t cidx;
+        if (!ops_claim_of(a.geo, page, sl, q, cidx)) continue;
+        const uint32_t word = a.geo.bitmap[(uint64_t)sl * a.geo.words_per_slot + (q >> 5)];
+        if ((word >> (q & 31u)) & 1u) continue;  // written before the queue: nobody sets it again
+        atomicMin(a.geo.claim + cidx, 2u * p.ord + p.kind);
+    }
+}
+
+// RESOLVE: the write pairs of the batches that bid, after every BID launch.  A
+// whole cover that finds its own key is the page's first setter: no paste lands
+// there, and the pair puts all-ones back.  A partial cover that finds the key of
+// a paste of a HIGHER ordinal is contested: in the per-batch sequence that paste
+// would bury the write, here the write lands on the pasted bytes.  The resets
+// run beside these reads, and harmlessly: a word being reset holds a write key
+// (even) or all-ones, and neither counts.  One LDS add a wave and one global
+// add a workgroup: the kernel is so short that every wave's add to the one
+// counter arrived at once, and 8,192 of them in a row took most of its time
+// (measured: DESIGN 6a, "Pastes inside the queue").
+__global__ __launch_bounds__(64 * kOpsWaves) void ops_resolve_kernel(OpsLaunch a) {
+    __shared__ uint32_t block_contested;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t S = (((a.n_pairs + 15u) >> 4) + 3u) >> 2;
+    if (blockIdx.x >= S) return;  // (uniform over the workgroup)
+    if (threadIdx.x == 0) block_contested = 0;
+    __syncthreads();
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    uint32_t ncontested = 0;  // uniform
+    for (uint64_t s = (uint64_t)wave * gridDim.x + blockIdx.x; s < S; s += (uint64_t)gridDim.x * kOpsWaves) {
+        const OpsPair p = ops_pair_of(a, s, S, lane);
+        const bool ok = p.on && p.kind == kOpWrite && ops_write_ok(a, p.d);
+        const uint64_t page = (p.d.dst >> a.page_shift) + p.k;
+        const bool touched = ok && page <= (p.d.dst + p.d.len - 1u) >> a.page_shift;
+        const bool whole = touched && (page << a.page_shift) >= p.d.dst && ((page + 1u) << a.page_shift) <= p.d.dst + p.d.len;
+        bool hit = false;
+        uint32_t sl, q;
+        uint64_t cidx;
+        if (touched && ops_claim_of(a.geo, page, sl, q, cidx)) {
+            const uint32_t v = __hip_atomic_load(a.geo.claim + cidx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (whole) {
+                if (v == 2u * p.ord)
+                    __hip_atomic_store(a.geo.claim + cidx, 0xFFFFFFFFu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            } else {
+                hit = v != 0xFFFFFFFFu && (v & 1u) && (v >> 1) > p.ord;
+            }
+        }
+        ncontested += (uint32_t)__popcll(__ballot(hit));
+    }
+    if (lane == 0 && ncontested) atomicAdd(&block_contested, ncontested);
+    __syncthreads();
+    if (threadIdx.x == 0 && block_contested && a.contested) atomicAdd(a.contested, (unsigned long long)block_contested);
+}
+
+// PASTE: the pairs of the paste batches, after every RESOLVE launch.  The pair
+// that finds its own key in the claim word is the page's winner; the wave walks
+// its winners by ballot, one page ahead of the hash: the source page is loaded from the
+// winner's batch's buffer (the descriptor read with a uniform index), hashed as
+// it passes through the registers and stored; the winner's own lane then writes
+// the CRC, ORs the bit, counts the page on its entry and puts all-ones back.
+// Every other pair moves no page.  paste_kernel's argument holds: a loser reads
+// the winner's key or all-ones, never its own (only the pairs of entry e ever
+// write e's key, one page each, and only the pair that found it resets it).
+template <int M>
+__global__ __launch_bounds__(64 * kOpsWaves) void ops_paste_kernel(OpsLaunch a) {
+    __shared__ uint32_t tab[kLdsBytes / 4];
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t S = (((a.n_pairs + 15u) >> 4) + 3u) >> 2;
+    if (blockIdx.x >= S) return;  // (uniform over the workgroup)
+    fill_lds<64 * kOpsWaves>(tab, static_cast<const uint4*>(a.image));
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t c0 = lane << 2 & 0x7Cu;
+    const uint32_t c1 = c0 | 0x10000u;
+    const uint32_t cf = kFinBase + (lane << 2);
+    uint32_t npasted = 0;  // uniform
+    for (uint64_t s = (uint64_t)wave * gridDim.x + blockIdx.x; s < S; s += (uint64_t)gridDim.x * kOpsWaves) {
+        const OpsPair p = ops_pair_of(a, s, S, lane);
+        const bool ok = p.on && p.kind == kOpPaste && !ops_paste_bad(a, p.d, p.src_bytes) &&
+                        p.k < (p.d.len >> a.page_shift);
+        const uint64_t page = (p.d.dst >> a.page_shift) + p.k;
+        const uint64_t from = p.d.src + ((uint64_t)p.k << a.page_shift);  // < src_bytes for a valid pair
+        bool win = false;
+        uint32_t sl = 0, q = 0;
+        uint64_t cidx = 0;
+        if (ok && ops_claim_of(a.geo, page, sl, q, cidx)) win = a.geo.claim[cidx] == 2u * p.ord + kOpPaste;
+        uint64_t todo = __ballot(win);
+        npasted += (uint32_t)__popcll(todo);
+        if (!todo) continue;
+        // the winners in lane order, one page ahead: the next winner's page is on its way
+        // while this one is hashed and stored
+        auto src_of = [&](uint32_t b) {
+            const uint32_t h = __builtin_amdgcn_readlane(p.h, b);
+            return reinterpret_cast<const uint32_t*>(a.b[h].src + readlane64(from, b)) + lane;
+        };
+        uint32_t b = (uint32_t)__builtin_ctzll(todo);
+        todo &= todo - 1ull;
+        uint32_t cur[M], nxt[M];
+        load_page<M>(cur, src_of(b));
+        for (;;) {
+            const bool more = todo != 0ull;
+            const uint32_t bn = more ? (uint32_t)__builtin_ctzll(todo) : b;
+            todo &= todo - 1ull;  // (0 stays 0)
+            if (more) load_page<M>(nxt, src_of(bn));
+            const uint32_t r = wave_xor(apply_fin(tab, chain<M>(tab, cur, c0, c1), cf)) ^ a.kconst;
+            store_page<M>(cur, a.pool + (readlane64(page, b) << (a.page_shift - 2u)) + lane);
+            uint32_t* per = a.b[__builtin_amdgcn_readlane(p.h, b)].pasted_per_entry;
+            if (lane == b) {  // the winner's own lane: its page, slot, entry
+                a.page_crcs[page] = r;
+                atomicOr(a.geo.bitmap + (uint64_t)sl * a.geo.words_per_slot + (q >> 5), 1u << (q & 31u));
+                atomicAdd(per + p.i, 1u);
+                __hip_atomic_store(a.geo.claim + cidx, 0xFFFFFFFFu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            if (!more) break;
+#pragma unroll
+            for (int j = 0; j < M; j++) cur[j] = nxt[j];
+            b = bn;
+        }
+    }
+    if (npasted && lane == 0 && a.pasted) atomicAdd(a.pasted, (unsigned long long)npasted);
+}
+
 // cc_clone_check_reads_dev: Read's NextClearBit test for a batch.  Every page a
 // read touches that lies in a clone chunk with a clear bit counts on its read;
 // a read past the pool is marked by the lane that loads it.
@@ -4165,6 +4390,45 @@ hipError_t launch_logs_prepass(const LogsPrepassLaunch& a, hipStream_t s) {
         default: return hipErrorInvalidValue;
     }
 #undef CC_PPCASE
+    return hipGetLastError();
+}
+
+static bool ops_launch_ok(const OpsLaunch& a) {
+    if (a.n_batches == 0 || a.n_batches > (uint32_t)kOpsBatches || a.n_pairs == 0 || a.blocks <= 0) return false;
+    if (a.page_bytes != 1u << a.page_shift || a.page_shift < 8 || a.geo.pages_per_chunk == 0 || !a.geo.clone_slot) return false;
+    for (uint32_t h = 0; h < a.n_batches; h++)
+        if ((a.b[h].kind == kOpPaste ? a.paste_slots : a.slots) == 0) return false;
+    return true;
+}
+
+hipError_t launch_ops_bid(const OpsLaunch& a, hipStream_t s) {
+    if (!ops_launch_ok(a)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(ops_bid_kernel, dim3(a.blocks), dim3(64 * kOpsWaves), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_ops_resolve(const OpsLaunch& a, hipStream_t s) {
+    if (!ops_launch_ok(a)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(ops_resolve_kernel, dim3(a.blocks), dim3(64 * kOpsWaves), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_ops_paste(const OpsLaunch& a, hipStream_t s) {
+    if (!ops_launch_ok(a)) return hipErrorInvalidValue;
+#define CC_OPCASE(MM)                                                                              \
+    case MM:                                                                                       \
+        hipLaunchKernelGGL((ops_paste_kernel<MM>), dim3(a.blocks), dim3(64 * kOpsWaves), 0, s, a); \
+        break;
+    switch (a.page_bytes / kWaveBytes) {
+        CC_OPCASE(1)
+        CC_OPCASE(2)
+        CC_OPCASE(4)
+        CC_OPCASE(8)
+        CC_OPCASE(16)
+        CC_OPCASE(32)
+        default: return hipErrorInvalidValue;
+    }
+#undef CC_OPCASE
     return hipGetLastError();
 }
 

@@ -600,11 +600,124 @@ int cc_clone_mark_dev(uint64_t pool_bytes, uint32_t page_bytes, const cc_update*
  * then one plain cc_apply_log*_dev per batch.  needCow is decided per chunk per
  * CALL, as in cc_apply_log_cow_dev: the caller splits a queue at the request
  * that creates a snapshot.  The caller must not run another call over the same
- * slots or bitmaps on another stream at the same time.  Not covered: Paste
- * inside the queue. */
+ * slots or bitmaps on another stream at the same time.  Paste inside the queue:
+ * cc_apply_ops_dev. */
 int cc_apply_logs_cow_dev(void* d_pool, uint64_t pool_bytes, uint32_t page_bytes, const cc_log_batch* batches,
                           uint32_t n_batches, uint32_t max_len, uint32_t* d_page_crcs, int delta, void* d_work,
                           uint64_t work_bytes, void* stream, const cc_cow* cow, const cc_clone* clone);
+
+/* The queue with PASTE BATCHES in it: a chunkserver's whole apply loop in one
+ * call.  In the reference a paste is a raft op like a write
+ * (PasteChunkInternalRequest::OnApply, op_request.cpp:725-747) and sits in the
+ * same apply queue, in log order; a lazily cloned volume produces them all the
+ * time (every clone read of a never-written region pastes what it fetched, and
+ * CHUNK_OP_RECOVER does nothing else).  ops[0..n_ops) is a HOST array (device
+ * pointers valid until the stream has run the call's work) of batches in queue
+ * order, each a write log (CC_OP_WRITE: d_src, d_recs, n as cc_log_batch) or a
+ * paste batch (CC_OP_PASTE: d_src, src_bytes, d_recs, n, d_pasted_per_entry as
+ * cc_paste_dev's arguments); empty batches are skipped.
+ *
+ * THE SEQUENCE this call stands for: per batch, in order, on `stream` --
+ *   write:  cc_apply_log_cow_dev(batch, delta, cow), then cc_clone_mark_dev(batch's log, max_len, clone);
+ *   paste:  cc_paste_dev(batch).
+ *
+ * THE MODEL this call computes.  Number the entries of all batches 0, 1, 2, ...
+ * in queue order: an entry's ORDINAL.  For a page p of a clone chunk whose bit is
+ * clear before the call, p's FIRST SETTER is the lowest-ordinal entry that is a
+ * valid paste entry covering p or a valid write entry covering p WHOLE.
+ *   1. Every page whose first setter is a paste entry is pasted as cc_paste_dev
+ *      pastes it: that entry's bytes, a fresh CRC in d_page_crcs, the bit set,
+ *      +1 on the entry's d_pasted_per_entry word and on *clone->d_pasted.
+ *   2. Then the write batches run, in order, as cc_apply_logs_cow_dev(write
+ *      batches, delta, cow, clone) runs them.
+ * The call leaves the pool, d_page_crcs, the snapshot arrays, the clone bitmaps,
+ * every d_pasted_per_entry, *clone->d_pasted and *d_contested exactly so.
+ *
+ * Relation to the sequence.  Which entry pastes a page is the same in both (the
+ * pre-queue bits and the records decide it, never bytes), so the bitmaps, every
+ * d_pasted_per_entry word and *d_pasted are ALWAYS those of the sequence.  A
+ * (write entry, page) pair is CONTESTED when the valid write entry touches p
+ * without covering it whole and p's first setter is a paste entry of a higher
+ * ordinal.  *d_contested += the number of such pairs (d_contested may be NULL).
+ * With no contested pair the result equals the sequence's bit for bit, in full
+ * and in delta mode: nothing reads or writes p, its CRC word or its bit before
+ * its paste, and the pasted page gets a fresh CRC before any delta touches it.
+ * On a contested page the bytes and the CRC word differ, and nothing else: the
+ * sequence lets the later paste bury the partial write; here the partial write
+ * lands on top of the origin data (origin bytes with the queue's writes applied
+ * in order), which is what a lazy clone should hold.  The reference accepts only
+ * block-aligned writes, so it has no contested pair.
+ *
+ * Per entry.  Write: the write log's rule, unchanged (1 <= len <= max_len, dst <
+ * pool_bytes, len <= pool_bytes - dst; else skipped whole).  Paste:
+ * cc_paste_dev's four rules (dst and len page multiples; inside the pool; src
+ * 4-byte aligned; src + len <= src_bytes) and len <= max_paste_len, a multiple of
+ * page_bytes, which makes a paste batch's (entry, page) pair space static as
+ * max_len does for writes.  An invalid paste entry gets UINT32_MAX in its word,
+ * bids for nothing and writes nothing; len == 0 is valid and inert.
+ *
+ * d_claim: all 0xFFFFFFFF on entry, and left so by every completed call.
+ *
+ * Reductions.  A queue with no non-empty paste batch IS cc_apply_logs_cow_dev
+ * over its write batches: same code path, same launches (clone and
+ * max_paste_len are then not needed).  With paste batches, the launches after
+ * the new passes are exactly those of cc_apply_logs_cow_dev over the write
+ * batches.  The passes, all on `stream`, each kind finished over all its
+ * launches before the next begins, 32 batch descriptors a launch riding in the
+ * kernel argument (no caller memory, no host-to-device copy, no allocation):
+ *   BID      a lane per (entry, page) pair of batches 0 .. the last paste batch:
+ *            a paste pair, and a write pair that covers its page whole, bids with
+ *            atomicMin(d_claim[page], 2 x ordinal + kind) where the page's chunk
+ *            is a clone and its bit is clear; marks invalid paste entries; reads
+ *            bitmaps, writes none.  (Later writes cannot change a winner.)
+ *   RESOLVE  the write pairs of those batches: a pair that finds its own key
+ *            puts all-ones back; a partial cover that finds the key of a paste of
+ *            a higher ordinal counts one contested pair.
+ *   PASTE    the pairs of all paste batches: the pair that finds its own key
+ *            loads its source page, hashes it in registers, stores it, writes
+ *            the CRC, ORs the bit, counts and resets the claim word.
+ * d_work / work_bytes: as for cc_apply_logs_dev, sized by the largest WRITE
+ * batch (not needed without write entries).  Measured: what the call
+ * saves is per paste batch, so it pays for the small, frequent paste batches of
+ * clone reads; PASTE moves pages about 7 % slower than cc_paste_dev's second
+ * launch, so a paste batch as large as a write batch is as well served by its
+ * own cc_paste_dev call between two queues.
+ *
+ * A chunk that carries both a snapshot slot and a clone slot is a caller error
+ * (cc_apply_logs_cow_dev).  Here the paste passes run first and the queue's
+ * copy-on-write pass after them, so such a chunk's snapshot would hold pasted
+ * pages; every access stays inside the arrays either way.
+ *
+ * Checked before a device is needed (CC_EINVAL): cc_apply_logs_cow_dev's checks
+ * on the write batches, cow and clone; per non-empty paste batch cc_paste_dev's
+ * (d_src, d_recs, d_pasted_per_entry non-NULL, d_src 4-byte aligned), and with
+ * one such batch: d_pool and d_page_crcs non-NULL, d_pool 4-byte aligned,
+ * pool_bytes whole pages, clone required (cc_paste_dev's checks on it),
+ * max_paste_len a non-zero multiple of page_bytes, and n x (max_paste_len /
+ * page_bytes) < 2^32 per paste batch (a batch's pairs are indexed in 32 bits);
+ * a kind other than the two; reserved != 0; ops NULL with n_ops > 0; the entries
+ * of all batches together >= 2^31 - 1 (ordinals live in d_claim).  n_ops == 0,
+ * or only empty batches: CC_OK.  No GPU: CC_ENODEV, never a CPU fallback.  The
+ * caller must not run another call over the same bitmaps on another stream at
+ * the same time, nor enqueue one on the same stream from another thread while
+ * this call enqueues (its passes and the queue's launches must reach the stream
+ * as one group, as a cc_paste_dev call's two launches must).  Not covered:
+ * sequence-exact bytes on contested pages. */
+#define CC_OP_WRITE 0u
+#define CC_OP_PASTE 1u
+typedef struct cc_op_batch {
+    uint32_t kind;                 /* CC_OP_WRITE | CC_OP_PASTE */
+    uint32_t reserved;             /* 0 */
+    const void* d_src;             /* the batch's data / origin buffer */
+    uint64_t src_bytes;            /* paste: bounds of d_src (cc_paste_dev's rule); write: ignored */
+    const cc_update* d_recs;       /* records, in order */
+    uint64_t n;
+    uint32_t* d_pasted_per_entry;  /* paste: [n], zeroed by the caller; write: ignored */
+} cc_op_batch;
+int cc_apply_ops_dev(void* d_pool, uint64_t pool_bytes, uint32_t page_bytes, const cc_op_batch* ops, uint32_t n_ops,
+                     uint32_t max_len, uint32_t max_paste_len, uint32_t* d_page_crcs, int delta, void* d_work,
+                     uint64_t work_bytes, void* stream, const cc_cow* cow, const cc_clone* clone,
+                     uint64_t* d_contested /* optional */);
 
 /* The NextClearBit test of CSChunkFile::Read on a clone chunk
  * (chunkserver_chunkfile.cpp:510-526: a range with any clear bit is refused
