@@ -121,6 +121,20 @@ class CcRepairCounts(ctypes.Structure):
     _fields_ = [("clean", _u32), ("repaired", _u32), ("failed", _u32), ("shadowed", _u32)]
 
 
+class CcScrubCounts(ctypes.Structure):
+    """cc_scrub_counts (include/curve_crc.h): the six running counts of cc_scrub_dev."""
+    _fields_ = [("live_checked", _u64), ("live_bad", _u64), ("snap_checked", _u64), ("snap_bad", _u64),
+                ("unwritten", _u64), ("listed", _u64)]
+
+
+class CcScrubChunk(ctypes.Structure):
+    """cc_scrub_chunk: a chunk's mismatching live and snapshot pages."""
+    _fields_ = [("live_bad", _u32), ("snap_bad", _u32)]
+
+
+CC_SCRUB_SNAP = 1 << 63  # cc_scrub_dev list entry: the snapshot copy of pool page (entry & ~CC_SCRUB_SNAP)
+
+
 SIGNATURES = {
     "crc32c_value": (_u32, [_vp, _sz]),
     "crc32c_extend": (_u32, [_u32, _vp, _sz]),
@@ -185,6 +199,8 @@ SIGNATURES = {
     "cc_read_merge_dev": (_int, [_vp, _u64, _u32, _vp, _u64, _vp, ctypes.POINTER(CcClone), _vp, _vp, _u64, _vp, _vp,
                                  _u64, _vp, _vp, _vp, _vp, _vp]),
     "cc_repair_dev": (_int, [_vp, _u64, _u32, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cc_scrub_dev": (_int, [_vp, _u64, _u32, _u32, _vp, ctypes.POINTER(CcCow), ctypes.POINTER(CcClone), _vp, _vp, _u64,
+                            _vp, _vp]),
     "cc_comm_unique_id": (_int, [_vp, _sz]),
     "cc_comm_init": (_int, [ctypes.POINTER(_vp), _int, _int, _vp, _sz]),
     "cc_comm_init_timeout": (_int, [ctypes.POINTER(_vp), _int, _int, _vp, _sz, _u32]),

@@ -1316,6 +1316,108 @@ def repair_pages(pool, page_crcs, pages, fetchers, claim, expect=None, page_byte
     return pg, cls, by
 
 
+SCRUB_SNAP = _lib.CC_SCRUB_SNAP  # scrub list entry: the snapshot copy of pool page (entry & ~SCRUB_SNAP)
+SCRUB_COUNTS = ("live_checked", "live_bad", "snap_checked", "snap_bad", "unwritten", "listed")
+
+
+def scrub_records(pool, page_crcs, chunk_bytes: int, counts, bad_list, bad_per_chunk=None, cow: Optional[Cow] = None,
+                  clone: Optional[Clone] = None, page_bytes: int = PAGE_SIZE, stream=None):
+    """cc_scrub_dev on buffers already resident on the device: the integrity
+    pass over `pool` as the datastore sees it.  Every live page that exists (not
+    a never-written page of a clone chunk of `clone`) is hashed against
+    `page_crcs`, every snapshot page that exists (its bit set in a slot of `cow`
+    that a chunk names) against cow.snap_crcs; never-written pages are counted
+    and not read.  `counts` int64 [6] gets += (SCRUB_COUNTS: live_checked,
+    live_bad, snap_checked, snap_bad, unwritten, listed); every mismatch takes
+    the next list position from `listed` and, while it is below
+    bad_list.numel(), stores its entry there (`bad_list` int64, or None for no
+    list: the pool page, | SCRUB_SNAP -- the sign bit -- for a snapshot copy);
+    `bad_per_chunk` int32 [chunks, 2] (optional) gets += (live_bad, snap_bad).
+    Reads the pool, the tables and the bitmaps only.  No host sync."""
+    torch = _torch()
+    nb = _nbytes(pool)
+    if page_bytes <= 0 or nb % page_bytes:
+        raise CurveCrcError(_lib.CC_EINVAL, "pool size is not a multiple of page_bytes")
+    if page_crcs.numel() * page_bytes < nb or page_crcs.element_size() != 4:
+        raise CurveCrcError(_lib.CC_EINVAL, "page_crcs must hold one 32-bit CRC per pool page")
+    if counts.numel() < 6 or counts.element_size() != 8:
+        raise CurveCrcError(_lib.CC_EINVAL, "counts must hold six 64-bit words")
+    if bad_list is not None and bad_list.element_size() != 8:
+        raise CurveCrcError(_lib.CC_EINVAL, "bad_list must hold 64-bit words")
+    if bad_per_chunk is not None and (chunk_bytes <= 0 or bad_per_chunk.element_size() != 4 or
+                                      bad_per_chunk.numel() * chunk_bytes < 2 * nb):
+        raise CurveCrcError(_lib.CC_EINVAL, "bad_per_chunk must hold two 32-bit words per chunk")
+    ws = cow.struct() if cow is not None else None
+    cs = clone.struct() if clone is not None else None
+    max_list = bad_list.numel() if bad_list is not None else 0
+    with torch.cuda.device(pool.device):
+        check(lib().cc_scrub_dev(_dev_ptr(pool, "pool"), nb, page_bytes, chunk_bytes, _dev_ptr(page_crcs, "page_crcs"),
+                                 ctypes.byref(ws) if ws is not None else None,
+                                 ctypes.byref(cs) if cs is not None else None, _dev_ptr(counts, "counts"),
+                                 _dev_ptr(bad_list, "bad_list") if max_list else None, max_list,
+                                 _dev_ptr(bad_per_chunk, "bad_per_chunk") if bad_per_chunk is not None else None,
+                                 _stream_handle(stream)), "cc_scrub_dev")
+    if stream is not None:
+        if cow is not None:
+            _record_cow(cow, stream)
+        if clone is not None:
+            _record_clone(clone, stream)
+
+
+class ScrubResult:
+    """What scrub() found: the six counts as attributes (SCRUB_COUNTS),
+    `live_bad_pages` / `snap_bad_pages` = sorted (chunk index, page in chunk)
+    pairs, and `per_chunk` = numpy int32 [chunks, 2] of (live_bad, snap_bad)."""
+
+    def __init__(self, counts, live_bad_pages, snap_bad_pages, per_chunk):
+        for name, v in zip(SCRUB_COUNTS, counts):
+            setattr(self, name, int(v))
+        self.live_bad_pages, self.snap_bad_pages, self.per_chunk = live_bad_pages, snap_bad_pages, per_chunk
+
+    @property
+    def clean(self) -> bool:
+        return self.live_bad == 0 and self.snap_bad == 0
+
+    def __repr__(self):
+        return "ScrubResult(" + ", ".join(f"{n}={getattr(self, n)}" for n in SCRUB_COUNTS) + ")"
+
+
+def scrub(pool, page_crcs, chunk_bytes: int, cow: Optional[Cow] = None, clone: Optional[Clone] = None,
+          max_bad: int = 4096, page_bytes: int = PAGE_SIZE, stream=None) -> ScrubResult:
+    """cc_scrub_dev: scrub `pool` (chunks of `chunk_bytes`) with its snapshot
+    slots `cow` and clone bitmaps `clone` (either may be None) and read the
+    result back.  Returns a ScrubResult.  Raises CC_ECORRUPT when more than
+    max_bad pages mismatch (the list cannot name them all), as
+    DevicePool.bad_pages does.  One host sync, on `stream`."""
+    import numpy as np
+    torch = _torch()
+    nb = _nbytes(pool)
+    if chunk_bytes <= 0 or nb % chunk_bytes:
+        raise CurveCrcError(_lib.CC_EINVAL, "pool size is not a multiple of chunk_bytes")
+    with _on_stream(stream):
+        counts = torch.zeros(6, dtype=torch.int64, device=pool.device)
+        lst = torch.full((max(1, max_bad),), -1, dtype=torch.int64, device=pool.device)
+        per = torch.zeros((max(1, nb // chunk_bytes), 2), dtype=torch.int32, device=pool.device)
+        scrub_records(pool, page_crcs, chunk_bytes, counts, lst[:max_bad] if max_bad else None, per, cow=cow,
+                      clone=clone, page_bytes=page_bytes, stream=stream)
+        if stream is not None:
+            for t in (counts, lst, per):
+                t.record_stream(stream)
+            stream.synchronize()  # the results were made on `stream`; the copies below run on the current one
+        cnt = counts.cpu().numpy()
+        listed = int(cnt[5])
+        if listed > max_bad:
+            raise CurveCrcError(_lib.CC_ECORRUPT, f"{listed} bad pages > max_bad={max_bad}")
+        ent = lst[:listed].cpu().numpy().view(np.uint64)
+        per_chunk = per[:nb // chunk_bytes].cpu().numpy()
+    ppc = chunk_bytes // page_bytes
+    snap = (ent >> np.uint64(63)).astype(bool)
+    pg = ent & np.uint64(SCRUB_SNAP - 1)
+    live_pages = sorted((int(p) // ppc, int(p) % ppc) for p in pg[~snap])
+    snap_pages = sorted((int(p) // ppc, int(p) % ppc) for p in pg[snap])
+    return ScrubResult(cnt, live_pages, snap_pages, per_chunk)
+
+
 def scan_files(paths, chunk_bytes: int = CHUNK_SIZE, meta_bytes: int = META_PAGE_SIZE,
                page_bytes: int = PAGE_SIZE, slice_bytes: int = SCAN_SIZE, io_threads: int = 0):
     """cc_scan_files: native pread + scan of chunk files.

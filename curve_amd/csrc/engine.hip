@@ -2375,6 +2375,92 @@ int cc_read_merge_dev(const void* d_pool, uint64_t pool_bytes, uint32_t page_byt
                                       }));
 }
 
+int cc_scrub_dev(const void* d_pool, uint64_t pool_bytes, uint32_t page_bytes, uint32_t chunk_bytes,
+                 const uint32_t* d_page_crcs, const cc_cow* cow, const cc_clone* clone, cc_scrub_counts* d_counts,
+                 uint64_t* d_bad_list, uint64_t max_list, cc_scrub_chunk* d_bad_per_chunk, void* stream) {
+    if (!log_page_ok(page_bytes)) return CC_EINVAL;
+    if (chunk_bytes == 0 || chunk_bytes % page_bytes || pool_bytes % chunk_bytes) return CC_EINVAL;
+    if (pool_bytes / page_bytes >= (1ull << 32)) return CC_EINVAL;
+    if (!d_pool || !d_page_crcs || !d_counts || ((uintptr_t)d_pool & 3u)) return CC_EINVAL;
+    if (max_list && !d_bad_list) return CC_EINVAL;
+    if (cow) {
+        if (cow->chunk_bytes != chunk_bytes) return CC_EINVAL;
+        if (!cow->d_snap_slot || !cow->d_snap || !cow->d_snap_crcs || !cow->d_snap_bitmap) return CC_EINVAL;
+        if ((uintptr_t)cow->d_snap & 3u) return CC_EINVAL;
+    }
+    if (clone && (clone->chunk_bytes != chunk_bytes || !clone->d_clone_slot || !clone->d_bitmap)) return CC_EINVAL;
+    if (pool_bytes == 0) return CC_OK;
+    CtxRef c;
+    int rc = get_ctx(&c);
+    if (rc) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const uint64_t n_pages = pool_bytes / page_bytes;
+    unsigned long long* counts = reinterpret_cast<unsigned long long*>(d_counts);
+    if (!cow && !clone) {
+        // the plain call: cc_page_verify_list_dev's launch with `listed` as its cursor
+        unsigned long long* first = nullptr;  // the page kernel's first-bad word: nobody reads it
+        hipError_t e = hipMallocAsync(reinterpret_cast<void**>(&first), 8, s);
+        if (e != hipSuccess) return map_err(e);
+        PageLaunch a = {};
+        a.pages = static_cast<const uint32_t*>(d_pool);
+        a.n_pages = n_pages;
+        a.words_per_lane = page_bytes / kWaveBytes;
+        a.image = c->image;
+        a.kconst = kconst_for(page_bytes);
+        a.expected = d_page_crcs;
+        a.sink.bad_count = counts + 5;
+        a.sink.first_bad = first;
+        a.sink.list = max_list ? reinterpret_cast<unsigned long long*>(d_bad_list) : nullptr;
+        a.sink.max_list = max_list;
+        a.sink.per_chunk = reinterpret_cast<uint32_t*>(d_bad_per_chunk);
+        a.sink.pages_per_chunk = chunk_bytes / page_bytes;
+        e = launch_scrub_plain(counts, n_pages, 0, s);
+        if (e == hipSuccess) e = launch_page_tail(c.get(), a, true, s);
+        if (e == hipSuccess) e = launch_scrub_plain(counts, n_pages, 1, s);
+        const hipError_t f = hipFreeAsync(first, s);
+        return map_err(e != hipSuccess ? e : f);
+    }
+    ScrubLaunch a = {};
+    a.pool = static_cast<const uint32_t*>(d_pool);
+    a.n_pages = n_pages;
+    a.n_index = cow ? 2 * n_pages : n_pages;
+    a.n_groups = (a.n_index + 63) / 64;
+    a.page_shift = (uint32_t)__builtin_ctz(page_bytes);  // a power of two (log_page_ok)
+    a.words_per_lane = page_bytes / kWaveBytes;
+    a.pages_per_chunk = chunk_bytes / page_bytes;
+    a.words_per_slot = (a.pages_per_chunk + 31) / 32;
+    const uint64_t m = snap_recip(a.pages_per_chunk);
+    a.ppc_mlo = (uint32_t)m;
+    a.ppc_mhi = (uint32_t)(m >> 32);
+    a.page_crcs = d_page_crcs;
+    if (cow) {
+        a.snap_n_slots = cow->n_slots;
+        a.snap_slot = cow->d_snap_slot;
+        a.snap = static_cast<const unsigned char*>(cow->d_snap);
+        a.snap_crcs = cow->d_snap_crcs;
+        a.snap_bitmap = cow->d_snap_bitmap;
+    }
+    if (clone) {
+        a.clone_n_slots = clone->n_slots;
+        a.clone_slot = clone->d_clone_slot;
+        a.clone_bitmap = clone->d_bitmap;
+    }
+    a.counts = counts;
+    a.list = reinterpret_cast<unsigned long long*>(d_bad_list);
+    a.max_list = max_list;
+    a.per_chunk = reinterpret_cast<uint32_t*>(d_bad_per_chunk);
+    a.image = c->image;
+    a.kconst = kconst_for(page_bytes);
+    a.blocks = c->cus;
+    return map_err(with_range_scratch(c.get(), s, 0,
+                                      [&](uint64_t* tiles, unsigned long long* tail, uint32_t*, uint32_t epoch) {
+                                          a.tiles = tiles;
+                                          a.tail = tail;
+                                          a.epoch = epoch;
+                                          return launch_scrub(a, s);
+                                      }));
+}
+
 // Streaming scan.  Each staging slot holds a batch of whole chunks (data and
 // metapages in separate device regions) plus the per-chunk results; a batch is
 // {H2D data+meta, page kernel over data, page kernel over metapages, fused

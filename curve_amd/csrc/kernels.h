@@ -34,6 +34,10 @@ struct VerifySink {
     unsigned long long* first_bad;
     unsigned long long* list;
     unsigned long long max_list;
+    // cc_scrub_dev with neither struct: a bad page also counts on its chunk,
+    // per_chunk[2 * (page / pages_per_chunk)] += 1 (null: no per-chunk words)
+    uint32_t* per_chunk;
+    uint32_t pages_per_chunk;
 };
 
 struct PageLaunch {
@@ -510,6 +514,48 @@ struct RepairLaunch {
 };
 hipError_t launch_repair_claim(const RepairLaunch& a, hipStream_t s);
 hipError_t launch_repair(const RepairLaunch& a, hipStream_t s);
+// Scrub (cc_scrub_dev): the integrity pass over the pages that EXIST.  The
+// domain is the live pages [0, n_pages) and, with a snapshot side, their
+// snapshot copies [n_pages, 2 n_pages), in groups of 64 indices on
+// verify-on-read's schedule (groups for reads).  A live page exists unless its
+// chunk is a clone chunk whose bit is clear (counted, never read); a snapshot
+// page exists when its chunk names a slot whose bit is set.  Every page that
+// exists is hashed against its table's word; nothing else moves.
+struct ScrubLaunch {
+    const uint32_t* pool;
+    uint64_t n_pages;            // pool pages (< 2^32)
+    uint64_t n_index;            // the domain: n_pages, or 2 n_pages with a snapshot side
+    uint64_t n_groups;           // ceil(n_index / 64)
+    uint32_t page_shift;         // log2(page_bytes)
+    uint32_t words_per_lane;     // page_bytes / 256
+    uint32_t pages_per_chunk;
+    uint32_t words_per_slot;     // bitmap words a slot: ceil(pages_per_chunk / 32)
+    uint32_t ppc_mlo, ppc_mhi;   // snap_recip(pages_per_chunk)
+    const uint32_t* page_crcs;
+    // the snapshot side (cc_cow); snap_slot null: none
+    uint32_t snap_n_slots;
+    const uint32_t* snap_slot;
+    const unsigned char* snap;
+    const uint32_t* snap_crcs;
+    const uint32_t* snap_bitmap;
+    // the clone side (cc_clone); clone_slot null: none
+    uint32_t clone_n_slots;
+    const uint32_t* clone_slot;
+    const uint32_t* clone_bitmap;
+    unsigned long long* counts;  // cc_scrub_counts: live_checked, live_bad, snap_checked, snap_bad, unwritten, listed
+    unsigned long long* list;    // [max_list] entries: page, or 2^63 | page for a snapshot copy
+    uint64_t max_list;
+    uint32_t* per_chunk;         // cc_scrub_chunk [chunks] {live_bad, snap_bad}, or null
+    uint64_t* tiles;             // the stream's range scratch, as ReadVerifyLaunch
+    unsigned long long* tail;
+    uint32_t epoch;
+    const void* image;
+    uint32_t kconst;
+    int blocks;                  // CUs
+};
+hipError_t launch_scrub(const ScrubLaunch& a, hipStream_t s);
+// the one-thread kernels around the page kernel when cc_scrub_dev has neither struct (kernels.hip scrub_plain_kernel)
+hipError_t launch_scrub_plain(unsigned long long* counts, uint64_t n_pages, int post, hipStream_t s);
 // CRC32C (butil Value) of arbitrary byte ranges of one device buffer, on the
 // flat block schedule, ONE launch: range_flat_kernel counts the
 // 4 KiB blocks of kRangeTiles contiguous tiles of the batch itself (epoch-tagged

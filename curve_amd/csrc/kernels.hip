@@ -124,6 +124,7 @@ __device__ __forceinline__ void emit(uint32_t crc, uint64_t page, uint32_t lane,
             const unsigned long long at = atomicAdd(vs.bad_count, 1ull);
             atomicMin(vs.first_bad, (unsigned long long)page);
             if (vs.list && at < vs.max_list) vs.list[at] = page;
+            if (vs.per_chunk) atomicAdd(vs.per_chunk + 2 * (page / vs.pages_per_chunk), 1u);
         }
     }
 }
@@ -155,6 +156,8 @@ __device__ __forceinline__ void flush_tile(uint32_t acc, uint64_t tile_first, ui
                 const unsigned long long idx = at + (unsigned long long)__popcll(bad & ((1ull << lane) - 1ull));
                 if (((bad >> lane) & 1ull) && idx < vs.max_list) vs.list[idx] = tile_first + lane;
             }
+            if (vs.per_chunk && ((bad >> lane) & 1ull))  // cc_scrub_dev's per-chunk words
+                atomicAdd(vs.per_chunk + 2 * ((tile_first + lane) / vs.pages_per_chunk), 1u);
         }
     }
 }
@@ -4039,6 +4042,297 @@ __global__ void xor_fold_kernel(const uint32_t* __restrict__ gathered, uint32_t 
     out[i] = v;
 }
 
+// ---------------------------------------------------------------------------
+// Scrub (cc_scrub_dev): the bulk integrity pass over a pool as the datastore
+// sees it.  The domain is [0, n_pages) -- the live pages -- and, with a cc_cow,
+// [n_pages, 2 n_pages) -- the snapshot copies of the same pool pages -- cut
+// into groups of 64 consecutive indices.  An index is PRESENT when its page
+// exists: a live page unless its chunk is a clone chunk whose bit is clear, a
+// snapshot page when its chunk names a slot whose bit is set.  Only present
+// pages move bytes; the groups sit on verify-on-read's schedule in the place
+// of reads (tile counts published by the waves, equal shares of present pages,
+// the last 1/16 dynamic).
+// ---------------------------------------------------------------------------
+// Set bits of a slot's bitmap in [q0, q1), q1 <= pages_per_chunk (so the unused
+// bits of the last word are never looked at).
+__device__ __forceinline__ uint32_t scrub_bits(const uint32_t* bm, uint32_t q0, uint32_t q1) {
+    uint32_t n = 0;
+    for (uint32_t wi = q0 >> 5; wi <= (q1 - 1u) >> 5; wi++) {
+        const uint32_t lo = q0 > wi * 32u ? q0 - wi * 32u : 0u;
+        const uint32_t hi = q1 < wi * 32u + 32u ? q1 - wi * 32u : 32u;
+        const uint32_t m = (hi == 32u ? 0xFFFFFFFFu : (1u << hi) - 1u) & ~((1u << lo) - 1u);
+        n += (uint32_t)__popc(bm[wi] & m);
+    }
+    return n;
+}
+struct ScrubCount {
+    uint64_t live, snap, unwritten;  // present live pages, present snapshot pages, never-written pages
+};
+// The counts of the pool pages [p0, p1) of one half (per lane; chunk by chunk, a bitmap word at a time)
+__device__ __forceinline__ void scrub_count_half(const ScrubLaunch& a, bool snap, uint32_t p0, uint64_t p1, ScrubCount& r) {
+    uint64_t p = p0;
+    while (p < p1) {
+        const uint32_t c = (uint32_t)p / a.pages_per_chunk;
+        const uint32_t q0 = (uint32_t)p - c * a.pages_per_chunk;
+        const uint64_t left = p1 - p;
+        const uint32_t q1 = left < a.pages_per_chunk - q0 ? q0 + (uint32_t)left : a.pages_per_chunk;
+        const uint32_t seg = q1 - q0;
+        if (snap) {
+            const uint32_t s = a.snap_slot[c];
+            if (s < a.snap_n_slots) r.snap += scrub_bits(a.snap_bitmap + (uint64_t)s * a.words_per_slot, q0, q1);
+        } else {
+            const uint32_t cs = a.clone_slot ? a.clone_slot[c] : 0xFFFFFFFFu;
+            if (cs < a.clone_n_slots) {
+                const uint32_t w = scrub_bits(a.clone_bitmap + (uint64_t)cs * a.words_per_slot, q0, q1);
+                r.live += w;
+                r.unwritten += seg - w;
+            } else {
+                r.live += seg;
+            }
+        }
+        p += seg;
+    }
+}
+// The counts of group g (indices [64 g, 64 g + 64) of the domain), per lane
+__device__ __forceinline__ ScrubCount scrub_group_count(const ScrubLaunch& a, uint64_t g) {
+    ScrubCount r = {0, 0, 0};
+    const uint64_t lo = g * 64, hi = lo + 64 < a.n_index ? lo + 64 : a.n_index;
+    if (lo < a.n_pages) scrub_count_half(a, false, (uint32_t)lo, hi < a.n_pages ? hi : a.n_pages, r);
+    if (hi > a.n_pages) scrub_count_half(a, true, (uint32_t)(lo > a.n_pages ? lo - a.n_pages : 0u), hi - a.n_pages, r);
+    return r;
+}
+__device__ __forceinline__ uint64_t wave_sum64(uint64_t v) {
+#pragma unroll
+    for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+// Tile t is the groups [G t / T, G (t+1) / T); its present pages, uniform.  `all`
+// also gets the tile's three counts (the counting pass of the tile's own wave).
+__device__ __forceinline__ uint64_t scrub_tile_count(const ScrubLaunch& a, uint32_t t, uint32_t lane, ScrubCount* all) {
+    const uint64_t lo = a.n_groups * t / kReadTiles, hi = a.n_groups * (t + 1) / kReadTiles;
+    ScrubCount s = {0, 0, 0};
+    for (uint64_t g = lo + lane; g < hi; g += 64) {
+        const ScrubCount r = scrub_group_count(a, g);
+        s.live += r.live;
+        s.snap += r.snap;
+        s.unwritten += r.unwritten;
+    }
+    const uint64_t present = wave_sum64(s.live + s.snap);
+    if (all) {
+        all->live += wave_sum64(s.live);
+        all->snap += wave_sum64(s.snap);
+        all->unwritten += wave_sum64(s.unwritten);
+    }
+    return present;
+}
+
+// One present page on its way through the hash: everything uniform.
+struct ScrubPg {
+    uint64_t src;   // its bytes
+    uint64_t idx;   // its index in the domain
+    uint32_t want;  // the stored CRC
+};
+
+// read_verify_kernel's schedule with groups in the place of reads.  A wave's
+// share is [lo, hi) of the present pages in domain order: the tile search in
+// registers, then the tile's groups 64 at a time (a lane counts one group from
+// the bitmap words) to the group holding page lo.  From there one lane
+// resolves one index -- slot word, bitmap word, source address -- and loads
+// its stored CRC (present lanes only: nothing of an absent page is read); the
+// ballot of the present lanes is the group's page list, walked with scalar
+// math across group boundaries so three register sets keep rotating for the
+// whole share.  The three counts a scrub owes for pages it never hashes leave
+// with the tile counts (each tile's own wave counts it once: one atomic a
+// count a wave); a mismatch costs its atomics on the spot.
+template <int M>
+__global__ __launch_bounds__(64 * kRvWaves) void scrub_kernel(ScrubLaunch a) {
+    __shared__ uint32_t tab[kLdsBytes / 4];
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint64_t Wg = (uint64_t)gridDim.x * kRvWaves;
+    const uint64_t w = (uint64_t)blockIdx.x * kRvWaves + wave;
+    const uint64_t tag = (uint64_t)a.epoch << kEpochShift;
+    const uint64_t G = a.n_groups;
+    {
+        ScrubCount mine = {0, 0, 0};
+        for (uint64_t t = w; t < kReadTiles; t += Wg) {
+            const uint64_t cnt = scrub_tile_count(a, (uint32_t)t, lane, &mine);
+            if (lane == 0) __hip_atomic_store(a.tiles + t, tag | cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        if (lane == 0) {
+            if (mine.live) atomicAdd(a.counts + 0, (unsigned long long)mine.live);
+            if (mine.snap) atomicAdd(a.counts + 2, (unsigned long long)mine.snap);
+            if (mine.unwritten) atomicAdd(a.counts + 4, (unsigned long long)mine.unwritten);
+        }
+    }
+    unsigned long long* dyn_ctr = a.tail + (a.epoch & 1u) * kDynCtrWords64;
+    if (blockIdx.x == 0 && threadIdx.x < kRvHeads)
+        atomicExch(a.tail + ((a.epoch + 1u) & 1u) * kDynCtrWords64 + threadIdx.x * kDynHeadStride, 0ull);
+    fill_lds<64 * kRvWaves>(tab, static_cast<const uint4*>(a.image));
+    const uint32_t c0 = lane << 2 & 0x7Cu;
+    const uint32_t c1 = c0 | 0x10000u;
+    const uint32_t cf = kFinBase + (lane << 2);
+
+    constexpr int kTpl = kReadTiles / 64;
+    uint64_t tb[kTpl];
+    wait_tiles<kTpl>(tb, a.tiles, tag, lane, [&](uint32_t t) { return scrub_tile_count(a, t, lane, nullptr); });
+    uint64_t lsum = 0;
+#pragma unroll
+    for (int j = 0; j < kTpl; j++) lsum += tb[j];
+    const uint64_t cum = wave_scan_incl(lsum, lane);
+    const uint64_t T = readlane64(cum, 63);
+    const uint64_t Wt = (T + kRvMinSlots - 1) / kRvMinSlots;
+    const uint64_t W = Wt < Wg ? (Wt ? Wt : 1) : Wg;
+    if ((uint64_t)blockIdx.x * kRvWaves >= W) return;  // uniform per block: no share, no tail
+    const uint64_t Ts = T - T / kRvDynDiv;
+    uint32_t dyn_head, dyn_tried;
+    tail_cursor<kRvHeads>(dyn_head, dyn_tried);
+    uint64_t lo_slot = w < W ? Ts * w / W : Ts, hi_slot = w < W ? Ts * (w + 1) / W : Ts;  // waves past W: tail only
+    uint32_t live_bad = 0, snap_bad = 0;
+    // a mismatch (rare; lane 0): the list cursor, the chunk's word
+    auto report = [&](const ScrubPg& p) {
+        const bool snap = p.idx >= a.n_pages;
+        const uint64_t pg = snap ? p.idx - a.n_pages : p.idx;
+        if (lane == 0) {
+            const unsigned long long at = atomicAdd(a.counts + 5, 1ull);
+            if (at < a.max_list) a.list[at] = snap ? (pg | (1ull << 63)) : pg;
+            if (a.per_chunk) atomicAdd(a.per_chunk + 2 * (pg / a.pages_per_chunk) + (snap ? 1u : 0u), 1u);
+        }
+        if (snap)
+            snap_bad++;
+        else
+            live_bad++;
+    };
+#pragma unroll 1
+    for (;;) {
+        if (lo_slot < hi_slot) {
+            // the group holding present page lo_slot, and the present pages before it
+            const TileHit th = tile_of(cum, tb, lo_slot, lane);
+            uint64_t g = G * th.tile / kReadTiles, S = th.before;
+            for (;;) {
+                const uint64_t gi = g + lane;
+                uint64_t cnt = 0;
+                if (gi < G) {
+                    const ScrubCount r = scrub_group_count(a, gi);
+                    cnt = r.live + r.snap;
+                }
+                const uint64_t c = wave_scan_incl(cnt, lane);
+                const uint64_t hit = __ballot(S + c > lo_slot);
+                if (hit) {
+                    const uint32_t l = (uint32_t)__builtin_ctzll(hit);
+                    S += l ? readlane64(c, l - 1) : 0;
+                    g += l;
+                    break;
+                }
+                S += readlane64(c, 63);
+                g += 64;
+                if (g >= G) break;  // the counts moved under the call (a caller error): nothing to walk
+            }
+            uint32_t skip = (uint32_t)(lo_slot - S);  // present pages of group g before the share (< 64)
+            uint64_t ke = hi_slot - lo_slot;          // pages to hash
+            // the page cursor: group gcur resolved a lane an index, `mask` its present lanes not yet taken
+            uint64_t gcur = g - 1, mask = 0;
+            uint64_t vsrc = 0;
+            uint32_t vwant = 0;
+            uint64_t fetched = 0;
+            ScrubPg last = {0, 0, 0};
+            // the next present page into p; none left: p = the last one (the same loads every step)
+            auto fetch = [&](ScrubPg& p) {
+                if (fetched < ke) {
+                    while (!mask) {
+                        if (++gcur >= G) break;
+                        const uint64_t idx = gcur * 64 + lane;
+                        bool present = false;
+                        if (idx < a.n_index) {
+                            const bool snap = idx >= a.n_pages;
+                            const uint32_t pg = (uint32_t)(snap ? idx - a.n_pages : idx);
+                            const uint32_t c = a.pages_per_chunk == 1
+                                                   ? pg
+                                                   : (uint32_t)(((uint64_t)pg * a.ppc_mhi + ((uint64_t)pg * a.ppc_mlo >> 32)) >> 32);
+                            const uint32_t q = pg - c * a.pages_per_chunk;
+                            if (snap) {
+                                const uint32_t s = a.snap_slot[c];
+                                if (s < a.snap_n_slots &&
+                                    ((a.snap_bitmap[(uint64_t)s * a.words_per_slot + (q >> 5)] >> (q & 31u)) & 1u)) {
+                                    const uint64_t sp = (uint64_t)s * a.pages_per_chunk + q;
+                                    present = true;
+                                    vsrc = (uint64_t)(uintptr_t)a.snap + (sp << a.page_shift);
+                                    vwant = a.snap_crcs[sp];
+                                }
+                            } else {
+                                const uint32_t cs = a.clone_slot ? a.clone_slot[c] : 0xFFFFFFFFu;
+                                if (cs >= a.clone_n_slots ||
+                                    ((a.clone_bitmap[(uint64_t)cs * a.words_per_slot + (q >> 5)] >> (q & 31u)) & 1u)) {
+                                    present = true;
+                                    vsrc = (uint64_t)(uintptr_t)a.pool + ((uint64_t)pg << a.page_shift);
+                                    vwant = a.page_crcs[pg];
+                                }
+                            }
+                        }
+                        mask = __ballot(present);
+                        for (; skip && mask; skip--) mask &= mask - 1;
+                    }
+                    if (mask) {
+                        const uint32_t j = (uint32_t)__builtin_ctzll(mask);
+                        mask &= mask - 1;
+                        last.src = readlane64(vsrc, j);
+                        last.want = (uint32_t)__builtin_amdgcn_readlane(vwant, j);
+                        last.idx = gcur * 64 + j;
+                        fetched++;
+                    } else {
+                        ke = fetched;  // ran off the domain (see above)
+                    }
+                }
+                p = last;
+            };
+            ScrubPg pA, pB, pC;
+            fetch(pA);
+            if (ke) {
+                fetch(pB);
+                pC = pB;
+                uint32_t A[M], B[M], Cq[M];
+                load_page<M>(A, reinterpret_cast<const uint32_t*>(pA.src) + lane);
+                load_page<M>(B, reinterpret_cast<const uint32_t*>(pB.src) + lane);
+                // hash X (page k of the share); page k+2's loads go into Y
+                auto step = [&](uint32_t (&X)[M], const ScrubPg& px, uint64_t k, uint32_t (&Y)[M], ScrubPg& py) {
+                    fetch(py);
+                    load_page<M>(Y, reinterpret_cast<const uint32_t*>(py.src) + lane);
+                    const uint32_t crc = wave_xor(apply_fin(tab, chain<M>(tab, X, c0, c1), cf)) ^ a.kconst;
+                    if (crc != px.want) report(px);
+                    return k + 1 < ke;
+                };
+                for (uint64_t k = 0;; k += 3) {
+                    if (!step(A, pA, k, Cq, pC)) break;
+                    if (!step(B, pB, k + 1, A, pA)) break;
+                    if (!step(Cq, pC, k + 2, B, pB)) break;
+                }
+            }
+        }
+        const uint64_t n_dyn = (T - Ts + kRvDynSlots - 1) / kRvDynSlots;
+        const uint64_t c = tail_pull<kRvHeads>(dyn_ctr, n_dyn, dyn_head, dyn_tried, lane);
+        if (c >= n_dyn) break;
+        lo_slot = Ts + c * kRvDynSlots;
+        hi_slot = lo_slot + kRvDynSlots < T ? lo_slot + kRvDynSlots : T;
+    }
+    if (lane == 0) {
+        if (live_bad) atomicAdd(a.counts + 1, (unsigned long long)live_bad);
+        if (snap_bad) atomicAdd(a.counts + 3, (unsigned long long)snap_bad);
+    }
+}
+
+// cc_scrub_dev with neither struct is the page kernel in verify mode, its
+// cursor the scrub's `listed`; these two one-thread kernels around it turn the
+// cursor's advance into live_bad (pre: live_bad -= listed, post: += listed,
+// mod 2^64) and count the pages, all of them checked.
+__global__ void scrub_plain_kernel(unsigned long long* counts, unsigned long long n_pages, int post) {
+    if (post) {
+        counts[1] += counts[5];
+        counts[0] += n_pages;
+    } else {
+        counts[1] -= counts[5];
+    }
+}
+
 // Fused metapages only ride a dynamic tail (the static walk knows one array).
 TailExtra tail_extra(const PageLaunch& a) {
     const bool meta = a.dyn_ctr && a.meta_pages && a.n_meta;
@@ -4498,6 +4792,30 @@ hipError_t launch_repair(const RepairLaunch& a, hipStream_t s) {
         default: return hipErrorInvalidValue;
     }
 #undef CC_FCASE
+    return hipGetLastError();
+}
+
+hipError_t launch_scrub(const ScrubLaunch& a, hipStream_t s) {
+    if (a.n_index == 0) return hipSuccess;
+#define CC_SCASE(MM)                                                                            \
+    case MM:                                                                                    \
+        hipLaunchKernelGGL((scrub_kernel<MM>), dim3(a.blocks), dim3(64 * kRvWaves), 0, s, a);   \
+        break;
+    switch (a.words_per_lane) {
+        CC_SCASE(1)
+        CC_SCASE(2)
+        CC_SCASE(4)
+        CC_SCASE(8)
+        CC_SCASE(16)
+        CC_SCASE(32)
+        default: return hipErrorInvalidValue;
+    }
+#undef CC_SCASE
+    return hipGetLastError();
+}
+
+hipError_t launch_scrub_plain(unsigned long long* counts, uint64_t n_pages, int post, hipStream_t s) {
+    hipLaunchKernelGGL(scrub_plain_kernel, dim3(1), dim3(1), 0, s, counts, (unsigned long long)n_pages, post);
     return hipGetLastError();
 }
 

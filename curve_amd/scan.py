@@ -178,6 +178,52 @@ class DevicePool:
             raise C.CurveCrcError(-74, f"{left} bad pages after the repair, {len(still)} expected")
         return repaired, still
 
+    def scrub(self, cow=None, clone=None, expected_page_crcs=None, max_bad: int = 4096, stream=None):
+        """The integrity pass over the pool as the datastore sees it
+        (C.scrub, cc_scrub_dev): the live pages that exist against
+        self.page_crcs (or `expected_page_crcs`), the snapshot pages that exist
+        in `cow` against its own CRCs, the never-written pages of the clone
+        chunks of `clone` counted and left unread.  Returns a C.ScrubResult;
+        raises if more than max_bad pages mismatch."""
+        table = self.page_crcs if expected_page_crcs is None else expected_page_crcs
+        return C.scrub(self.data, table, self.chunk_size, cow=cow, clone=clone, max_bad=max_bad,
+                       page_bytes=self.page_bytes, stream=stream)
+
+    def scrub_repair(self, fetchers, cow=None, clone=None, expected_page_crcs=None, max_bad: int = 4096, claim=None,
+                     stream=None):
+        """repair_bad_pages with the scrub as its detector and as its second
+        check, for a pool with snapshots and clone chunks: scrub, C.repair_pages
+        of the LIVE bad pages from `fetchers` in order (expect = the table the
+        scrub used), scrub again.  A never-written page is never reported, so
+        never fetched.  Snapshot bad pages are reported and NOT repaired:
+        cc_repair_dev writes the pool only, and a snapshot slot's page has no
+        peer range of its own in this interface.  Returns (repaired, still_bad,
+        snap_bad): repaired = [(chunk index, page in chunk, fetcher index)],
+        still_bad = [(chunk index, page in chunk)] of the live pages no peer
+        could mend, snap_bad = [(chunk index, page in chunk)] of the
+        mismatching snapshot copies, all sorted.  The second scrub's live_bad
+        must equal len(still_bad) and its snapshot pages the first's
+        (CC_ECORRUPT otherwise: the pool changed under the repair).  `claim` =
+        C.repair_claim(self.data), made here when None."""
+        ppc = self.chunk_size // self.page_bytes
+        table = self.page_crcs if expected_page_crcs is None else expected_page_crcs
+        with C._on_stream(stream):  # the counts are read back on the stream that made them
+            first = self.scrub(cow=cow, clone=clone, expected_page_crcs=table, max_bad=max_bad, stream=stream)
+            if not first.live_bad_pages:
+                return [], [], first.snap_bad_pages
+            if claim is None:
+                claim = C.repair_claim(self.data, self.page_bytes)
+            pages, cls, by = C.repair_pages(self.data, self.page_crcs, [c * ppc + q for c, q in first.live_bad_pages],
+                                            fetchers, claim, expect=table, page_bytes=self.page_bytes, stream=stream)
+            second = self.scrub(cow=cow, clone=clone, expected_page_crcs=table, max_bad=max_bad, stream=stream)
+        repaired = [(int(p) // ppc, int(p) % ppc, int(f)) for p, k, f in zip(pages, cls, by) if k == C.REPAIR_REPAIRED]
+        still = [(int(p) // ppc, int(p) % ppc) for p, k in zip(pages, cls) if k == C.REPAIR_FAILED]
+        if second.live_bad != len(still):
+            raise C.CurveCrcError(-74, f"{second.live_bad} bad live pages after the repair, {len(still)} expected")
+        if second.snap_bad_pages != first.snap_bad_pages:
+            raise C.CurveCrcError(-74, "the snapshot pages changed under the repair")
+        return repaired, still, first.snap_bad_pages
+
     # -- reference surfaces built on the device results ----------------------
     def scan_maps(self, logical_pool_id: int, copyset_id: int, first_index: int = 0) -> List[ScanMap]:
         """ScanMaps as ScanChunkRequest::OnApply builds them (op_request.cpp:795-803),

@@ -877,6 +877,85 @@ int cc_repair_dev(void* d_pool, uint64_t pool_bytes, uint32_t page_bytes, const 
                   const cc_update* d_reqs, uint64_t n, uint32_t* d_page_crcs, const uint32_t* d_expect,
                   uint32_t* d_claim, cc_repair_counts* d_per_entry, uint64_t* d_totals, void* stream);
 
+/* Scrub: the bulk integrity pass over a device pool AS THE DATASTORE SEES IT.
+ * cc_page_verify_list_dev hashes every pool page against d_page_crcs; a pool
+ * with clone chunks has pages that were never written (no meaningful bytes or
+ * CRC word: the datastore refuses to read them, PageNerverWrittenError,
+ * chunkserver_chunkfile.cpp:510-526), and a pool with open snapshots has pages
+ * in its snapshot slots that no bulk pass ever looks at.  This call checks the
+ * pages that EXIST, each against the table that describes it, and counts the
+ * rest.  It answers the ScanManager's pass (scan_manager.cpp:210-296) for a
+ * device-resident pool, snapshot copies included.
+ *
+ * Geometry: ppc = chunk_bytes / page_bytes; pool page p is chunk c = p / ppc,
+ * page q = p % ppc.
+ *
+ * LIVE pass, over every pool page p.  Let cs = clone ? d_clone_slot[c] :
+ * CC_NOT_CLONE.  If cs < clone->n_slots and bit q of slot cs is clear the page
+ * was NEVER WRITTEN: neither the page nor d_page_crcs[p] is read, unwritten
+ * += 1.  Otherwise the page is hashed whole against d_page_crcs[p]:
+ * live_checked += 1, and on a mismatch live_bad += 1,
+ * d_bad_per_chunk[c].live_bad += 1 and the list gets p.  A live page whose
+ * snapshot bit is set is still a live page and is checked: this call audits
+ * storage, it is not cc_read_snap_dev's snapshot view.
+ *
+ * SNAP pass, only with cow.  For every pool page p let s = d_snap_slot[c]; when
+ * s < cow->n_slots and bit q of slot s is set, the bytes at d_snap +
+ * (s * ppc + q) * page_bytes are hashed against d_snap_crcs[s * ppc + q]:
+ * snap_checked += 1, and on a mismatch snap_bad += 1,
+ * d_bad_per_chunk[c].snap_bad += 1 and the list gets CC_SCRUB_SNAP | p.  Nothing
+ * else of a slot is read: not a page whose bit is clear, not a slot that no
+ * chunk names, not a slot value >= n_slots.  Bits at positions >= ppc of a
+ * slot's last bitmap word are ignored, in both structs.  Two chunks naming one
+ * slot (a caller error in the datastore) are each scrubbed on their own terms.
+ *
+ * List: every mismatch does k = listed++ (the value before the call counts: a
+ * second call on the same counters continues the cursor) and stores its entry
+ * at d_bad_list[k] when k < max_list.  The entries come in no particular order,
+ * as cc_page_verify_list_dev's; listed may exceed max_list, and nothing is
+ * written at or past d_bad_list + max_list.  d_bad_list may be NULL only when
+ * max_list == 0.  When the mismatches fit, the SET of entries is deterministic;
+ * the six counts and the per-chunk words always are.  All counts are += (the
+ * caller zeroes them).
+ *
+ * Read-only: the call writes d_counts, d_bad_list and d_bad_per_chunk and
+ * nothing else -- not the pool, a CRC table, a bitmap, d_claim, d_copied,
+ * d_stale or d_pasted; d_claim and the counters of both structs may be NULL.
+ * The caller must not run a write log, a paste or a repair over the same pool
+ * on another stream at the same time.
+ *
+ * Checked before a device is needed (CC_EINVAL): page_bytes = 256 * 2^k
+ * (k = 0..5); chunk_bytes a non-zero multiple of page_bytes that divides
+ * pool_bytes; pool_bytes / page_bytes < 2^32; d_pool, d_page_crcs and d_counts
+ * non-NULL, d_pool 4-byte aligned; a non-zero max_list with a NULL list; with
+ * cow: its chunk_bytes == chunk_bytes, its slot, snap, CRC and bitmap pointers
+ * non-NULL, d_snap 4-byte aligned; with clone: its chunk_bytes == chunk_bytes,
+ * d_clone_slot and d_bitmap non-NULL.  pool_bytes == 0 is CC_OK.  No GPU:
+ * CC_ENODEV, never a CPU fallback.
+ *
+ * cow == NULL && clone == NULL IS cc_page_verify_list_dev: the page kernel, the
+ * same launch, its rate (the kernel's list cursor is `listed`, its mismatch
+ * path also counts the chunk's word; two one-thread launches around it fill
+ * live_checked and live_bad).  Otherwise ONE launch on verify-on-read's
+ * schedule with groups of 64 domain indices (the live pages, then their
+ * snapshot copies) in the place of reads: the kernel counts the pages that
+ * exist per tile of groups from the bitmap words, every wave hashes an equal
+ * share of them, the last 1/16 handed out dynamically, so the balance does not
+ * depend on where the sparse parts lie and a page that does not exist moves no
+ * bytes.  Uses the stream's range scratch the engine keeps: no caller work
+ * buffer. */
+#define CC_SCRUB_SNAP (1ull << 63) /* list entry: the SNAPSHOT copy of pool page (entry & ~CC_SCRUB_SNAP) */
+typedef struct cc_scrub_counts {   /* device memory, all += ; the caller zeroes */
+    uint64_t live_checked, live_bad, snap_checked, snap_bad, unwritten, listed;
+} cc_scrub_counts;
+typedef struct cc_scrub_chunk {
+    uint32_t live_bad, snap_bad;
+} cc_scrub_chunk;
+int cc_scrub_dev(const void* d_pool, uint64_t pool_bytes, uint32_t page_bytes, uint32_t chunk_bytes,
+                 const uint32_t* d_page_crcs, const cc_cow* cow, const cc_clone* clone, cc_scrub_counts* d_counts,
+                 uint64_t* d_bad_list, uint64_t max_list,
+                 cc_scrub_chunk* d_bad_per_chunk /* [pool_bytes / chunk_bytes], += , or NULL */, void* stream);
+
 /* One chunk file as the datastore holds it: metapage + data
  * (file = metapage || data, chunkserver_chunkfile.cpp:497-536). */
 typedef struct cc_chunk_src {
