@@ -612,6 +612,14 @@ __device__ __forceinline__ uint64_t wave_scan_incl(uint64_t v, uint32_t lane) {
     }
     return v;
 }
+__device__ __forceinline__ uint32_t wave_scan_incl(uint32_t v, uint32_t lane) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t o = __shfl_up(v, d, 64);
+        if (lane >= (uint32_t)d) v += o;
+    }
+    return v;
+}
 
 // Every tile count of this call into tb (lane l: tiles kTpl*l .. kTpl*l + kTpl-1):
 // poll the epoch-tagged words (sc1 loads: a data-tagged granule needs no
@@ -2107,22 +2115,32 @@ __device__ __forceinline__ uint64_t read_tile_count(const ReadVerifyLaunch& a, u
     return sum;
 }
 
-// Every page a read touches is one slot; the batch's slots are read 0's pages,
-// then read 1's, ...  ONE launch, scheduled as the range kernel is (§7): the
-// waves count kReadTiles tiles of reads themselves (epoch-tagged words, a
-// bounded wait) and hold the counts in registers; wave w owns the slots
-// [Ts w / W, Ts (w+1) / W) at PAGE granularity (a read may be split over
-// waves; its mismatches are counted by atomics), the last T / kRvDynDiv slots
-// are dynamic chunks.  A share starts at the read holding its first slot
-// (tile search in registers, then the tile's reads 64 at a time); the wave
-// takes its reads 64 at a time (lane j <- one read: first page, page count)
-// and lays their pages out as one stream with a wave prefix sum: page k of
-// the stream belongs to the first lane whose running count exceeds k (a
-// ballot), so the stream is walked with uniform scalar math only -- no loads
-// in the per-page path -- hashed with the next two pages' loads in flight
-// (three register sets rotating).  The stored CRCs come in with VECTOR loads
-// (an opaque zero in the address) so they never share lgkmcnt with the chain's
-// LDS lookups.  A mismatch is counted on its read (rare: atomics).
+// ---------------------------------------------------------------------------
+// The slot schedule and the group walk of the gathered page kernels.
+// rv_begin / rv_next: read_verify, snap_read, paste, scrub.  rv_walk: the first
+// three (scrub walks groups of pool pages with a cursor of its own).
+// merge_read_kernel and repair_kernel follow the same schedule and walk from
+// copies of their own (their comments say why): a change here is made there too.
+// ---------------------------------------------------------------------------
+// Every page an entry (a read, a paste, a repair request) touches is one slot;
+// the batch's slots are entry 0's pages, then entry 1's, ...  ONE launch,
+// scheduled as the range kernel is (§7): the waves count kReadTiles tiles of
+// entries themselves (epoch-tagged words, a bounded wait) and hold the counts
+// in registers; wave w owns the slots [Ts w / W, Ts (w+1) / W) at PAGE
+// granularity (an entry may be split over waves; what is counted on it is
+// counted by atomics), the last T / kRvDynDiv slots are dynamic chunks (the
+// page kernel's tail: the XCDs run at different rates).  The tail's counter is
+// slot epoch % 2 of the block; each call zeroes the other slot for the next.
+// A share starts at the entry holding its first slot (tile search in
+// registers, then the tile's entries 64 at a time); the wave takes its entries
+// 64 at a time (lane j <- one entry: first page, page count) and lays their
+// pages out as one stream with a wave prefix sum: page k of the stream belongs
+// to the first lane whose running count exceeds k (a ballot), so the stream is
+// walked with uniform scalar math only -- no loads in the per-page path --
+// and handled with the next two pages' loads in flight (three register sets
+// rotating, in each kernel's own body).  Table words and stored CRCs come in
+// with VECTOR loads (an opaque zero in the address) so they never share
+// lgkmcnt with the chain's LDS lookups.
 // (Rounds 2-3: a count kernel and rocPRIM's two-launch exclusive scan ran
 // first, 16-24 us of a 0.67 ms call.)
 constexpr int kRvWaves = 8;  // waves per CU of the verify-on-read kernel
@@ -2131,98 +2149,188 @@ constexpr uint32_t kRvHeads = 1;  // tail heads (A/B round 3: 8 per-XCD heads = 
 constexpr uint64_t kRvDynSlots = 32;  // slots (pages) per dynamic chunk (64: -1 %, 128: -5 %, 256: -18 % -- too coarse)
 constexpr uint64_t kRvMinSlots = 8;  // a small batch goes to the fewest waves that give each >= 8 page slots
 constexpr uint32_t kRvSmallMinSlots = 2;  // the one-launch path (<= 64 reads): >= 2 pages per wave
+
+// A wave's view of the schedule: every tile count of the call (lane l holds
+// tiles kTpl*l .. kTpl*l + kTpl-1, cum = inclusive prefix of the lane sums),
+// the totals, the tail's cursor and the share it is working on.
+struct RvShares {
+    uint64_t tb[kReadTiles / 64];
+    uint64_t cum;
+    uint64_t T, Ts, W;         // slots, statically dealt slots, waves sharing them
+    unsigned long long* ctr;   // the tail's counter
+    uint32_t head, tried;      // the tail's cursor (tail_cursor)
+    uint64_t lo_slot, hi_slot; // the current share
+};
+
+// From the tile-count publication to the wave's static share.  count(t, mark)
+// is the kernel's own tile count (mark: the counting pass of the tile's own
+// wave, which marks invalid entries; without it, a wave counting a missing
+// tile).  Fills the workgroup's LDS on the way (which hides the stores' and
+// the other workgroups' latency).  False for a workgroup with no share.
+template <typename Count>
+__device__ __forceinline__ bool rv_begin(RvShares& sh, uint32_t* tab, uint64_t* tiles, unsigned long long* tail,
+                                         uint32_t epoch, const void* image, uint32_t lane, Count count) {
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint64_t Wg = (uint64_t)gridDim.x * kRvWaves;
+    const uint64_t w = (uint64_t)blockIdx.x * kRvWaves + wave;
+    const uint64_t tag = (uint64_t)epoch << kEpochShift;
+    for (uint64_t t = w; t < kReadTiles; t += Wg) {
+        const uint64_t cnt = count((uint32_t)t, true);
+        if (lane == 0) __hip_atomic_store(tiles + t, tag | cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    sh.ctr = tail + (epoch & 1u) * kDynCtrWords64;
+    if (blockIdx.x == 0 && threadIdx.x < kRvHeads)
+        atomicExch(tail + ((epoch + 1u) & 1u) * kDynCtrWords64 + threadIdx.x * kDynHeadStride, 0ull);
+    fill_lds<64 * kRvWaves>(tab, static_cast<const uint4*>(image));
+    constexpr int kTpl = kReadTiles / 64;
+    wait_tiles<kTpl>(sh.tb, tiles, tag, lane, [&](uint32_t t) { return count(t, false); });
+    uint64_t lsum = 0;
+#pragma unroll
+    for (int j = 0; j < kTpl; j++) lsum += sh.tb[j];
+    sh.cum = wave_scan_incl(lsum, lane);
+    sh.T = readlane64(sh.cum, 63);
+    // W waves share the slots: all of the grid for a large batch, fewer for a small one
+    const uint64_t Wt = (sh.T + kRvMinSlots - 1) / kRvMinSlots;
+    sh.W = Wt < Wg ? (Wt ? Wt : 1) : Wg;
+    if ((uint64_t)blockIdx.x * kRvWaves >= sh.W) return false;  // uniform per block: no share, no tail
+    sh.Ts = sh.T - sh.T / kRvDynDiv;
+    tail_cursor<kRvHeads>(sh.head, sh.tried);
+    sh.lo_slot = w < sh.W ? sh.Ts * w / sh.W : sh.Ts;  // waves past W: tail only
+    sh.hi_slot = w < sh.W ? sh.Ts * (w + 1) / sh.W : sh.Ts;
+    return true;
+}
+
+// The next dynamic chunk of kRvDynSlots slots; false when the tail is drained.
+__device__ __forceinline__ bool rv_next(RvShares& sh, uint32_t lane) {
+    const uint64_t n_dyn = (sh.T - sh.Ts + kRvDynSlots - 1) / kRvDynSlots;
+    const uint64_t c = tail_pull<kRvHeads>(sh.ctr, n_dyn, sh.head, sh.tried, lane);
+    if (c >= n_dyn) return false;
+    sh.lo_slot = sh.Ts + c * kRvDynSlots;
+    sh.hi_slot = sh.lo_slot + kRvDynSlots < sh.T ? sh.lo_slot + kRvDynSlots : sh.T;
+    return true;
+}
+
+// What lane j holds of its entry in a group of 64, and slot k of the group's
+// page stream: the lane of its entry, its position in the entry, its pool page.
+struct RvEntry {
+    uint64_t pages;  // 0 for an entry that takes no slot (empty or invalid)
+    uint64_t p0;     // its first pool page
+};
+struct RvSlot {
+    uint32_t owner, rel;
+    uint64_t g;
+};
+__device__ __forceinline__ RvSlot slot_at(uint32_t cum32, uint64_t p0, uint32_t k) {
+    RvSlot s;
+    s.owner = (uint32_t)__builtin_ctzll(__ballot(cum32 > k));
+    s.rel = k - (s.owner ? (uint32_t)__builtin_amdgcn_readlane(cum32, s.owner - 1) : 0u);
+    s.g = readlane64(p0, s.owner) + s.rel;
+    return s;
+}
+
+// The share [lo_slot, hi_slot) at PAGE granularity: from the entry holding
+// slot lo_slot through the entries starting before hi_slot, cut at both ends.
+// entry(i) loads entry i for this lane (whatever else the kernel keeps of it,
+// such as an output offset, stays in the lambda's captures); body(base, cum32,
+// p0, ks, ke) handles slots [ks, ke) of the group of entries base .. base + 63,
+// cum32 their inclusive page counts.  The seek's last 64 descriptors are the
+// first group's: they are not loaded a second time.
+template <typename Entry, typename Body>
+__device__ __forceinline__ void rv_walk(const RvShares& sh, uint64_t n, uint32_t lane, Entry entry, Body body) {
+    if (sh.lo_slot >= sh.hi_slot) return;
+    auto load = [&](uint64_t base) {
+        const uint64_t i = base + lane;
+        RvEntry e = entry(i < n ? i : base);
+        if (i >= n) e.pages = 0;
+        return e;
+    };
+    const TileHit th = tile_of(sh.cum, sh.tb, sh.lo_slot, lane);
+    uint64_t base = n * th.tile / kReadTiles;  // the group's first entry
+    uint64_t S = th.before;                    // the slot of its page 0
+    RvEntry e;
+    // the tile's entries 64 at a time, to the group whose pages pass lo_slot
+    for (;;) {
+        e = load(base);
+        const uint64_t tot = readlane64(wave_scan_incl(e.pages, lane), 63);
+        if (S + tot > sh.lo_slot || base + 64 >= n) break;
+        S += tot;
+        base += 64;
+    }
+    for (bool first = true; base < n && S < sh.hi_slot; base += 64, first = false) {
+        if (!first) e = load(base);
+        const uint32_t cum32 = wave_scan_incl((uint32_t)e.pages, lane);
+        const uint32_t P = __builtin_amdgcn_readlane(cum32, 63);
+        const uint32_t ks = sh.lo_slot > S ? (uint32_t)(sh.lo_slot - S) : 0u;
+        const uint32_t ke = sh.hi_slot - S < (uint64_t)P ? (uint32_t)(sh.hi_slot - S) : P;
+        S += P;
+        if (ks < ke) body(base, cum32, e.p0, ks, ke);
+    }
+}
+
+// The one-launch path of the three read calls (<= 64 reads, one per lane): no
+// tiles and no scratch.  Every wave works out the batch's pages per read and
+// their wave prefix sum; entry(i, mark) loads read i as rv_walk's does (mark:
+// wave 0 of block 0, which marks the invalid ones).  The P pages are split
+// evenly over the fewest waves that give each >= kRvSmallMinSlots, at PAGE
+// granularity; the blocks left without pages exit before filling LDS.  False
+// for a wave without pages; otherwise it owns slots [k0, k1) of the stream.
+struct RvSmallShare {
+    uint32_t cum;  // inclusive page counts of the lanes' reads
+    uint64_t p0;   // the lane's read's first pool page
+    uint32_t k0, k1;
+};
+template <typename Entry>
+__device__ __forceinline__ bool rv_small_begin(RvSmallShare& sm, uint32_t* tab, const ReadVerifyLaunch& rv,
+                                               uint32_t lane, Entry entry) {
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const bool valid = lane < rv.n_reads;
+    const RvEntry e = entry(valid ? lane : 0u, valid && blockIdx.x == 0 && wave == 0);
+    sm.p0 = e.p0;
+    sm.cum = wave_scan_incl(valid ? (uint32_t)e.pages : 0u, lane);
+    const uint32_t P = __builtin_amdgcn_readlane(sm.cum, 63);
+    const uint32_t Wg = gridDim.x * kRvWaves, Wt = (P + kRvSmallMinSlots - 1) / kRvSmallMinSlots;
+    const uint32_t W = Wt < Wg ? Wt : Wg;
+    if (blockIdx.x * (uint32_t)kRvWaves >= W) return false;  // uniform per block (P == 0: every block)
+    fill_lds<64 * kRvWaves>(tab, static_cast<const uint4*>(rv.image));
+    const uint32_t w = blockIdx.x * kRvWaves + wave;
+    if (w >= W) return false;
+    sm.k0 = (uint32_t)((uint64_t)P * w / W);
+    sm.k1 = (uint32_t)((uint64_t)P * (w + 1) / W);
+    return sm.k0 < sm.k1;
+}
+
+// ---------------------------------------------------------------------------
+// cc_verify_reads_dev's kernels
+// ---------------------------------------------------------------------------
+// Per page: the stored CRC and the page are loaded two steps ahead, the page
+// is hashed and a mismatch is counted on its read (rare: atomics).
 template <int M>
 __global__ __launch_bounds__(64 * kRvWaves) void read_verify_kernel(ReadVerifyLaunch a) {
     __shared__ uint32_t tab[kLdsBytes / 4];
     const uint64_t n = a.n_reads;
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint64_t Wg = (uint64_t)gridDim.x * kRvWaves;
-    const uint64_t w = (uint64_t)blockIdx.x * kRvWaves + wave;
-    const uint64_t tag = (uint64_t)a.epoch << kEpochShift;
-    // this wave's tile counts, published before the LDS fill
-    for (uint64_t t = w; t < kReadTiles; t += Wg) {
-        const uint64_t cnt = read_tile_count(a, (uint32_t)t, lane, true);
-        if (lane == 0) __hip_atomic_store(a.tiles + t, tag | cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    // the tail's counter: slot epoch % 2; this call zeroes the other for the next
-    unsigned long long* dyn_ctr = a.tail + (a.epoch & 1u) * kDynCtrWords64;
-    if (blockIdx.x == 0 && threadIdx.x < kRvHeads)
-        atomicExch(a.tail + ((a.epoch + 1u) & 1u) * kDynCtrWords64 + threadIdx.x * kDynHeadStride, 0ull);
-    fill_lds<64 * kRvWaves>(tab, static_cast<const uint4*>(a.image));
+    RvShares sh;
+    if (!rv_begin(sh, tab, a.tiles, a.tail, a.epoch, a.image, lane,
+                  [&](uint32_t t, bool mark) { return read_tile_count(a, t, lane, mark); }))
+        return;
     const uint32_t c0 = lane << 2 & 0x7Cu;
     const uint32_t c1 = c0 | 0x10000u;
     const uint32_t cf = kFinBase + (lane << 2);
     const uint32_t* pages = a.pool + lane;
     uint32_t vz = 0;
     asm volatile("" : "+v"(vz));  // opaque zero: keeps uniform-address loads on the vector path
-
-    constexpr int kTpl = kReadTiles / 64;
-    uint64_t tb[kTpl];
-    wait_tiles<kTpl>(tb, a.tiles, tag, lane, [&](uint32_t t) { return read_tile_count(a, t, lane, false); });
-    uint64_t lsum = 0;
-#pragma unroll
-    for (int j = 0; j < kTpl; j++) lsum += tb[j];
-    const uint64_t cum = wave_scan_incl(lsum, lane);
-    const uint64_t T = readlane64(cum, 63);
-    // W waves share the slots: all of the grid for a large batch, fewer for a small one
-    const uint64_t Wt = (T + kRvMinSlots - 1) / kRvMinSlots;
-    const uint64_t W = Wt < Wg ? (Wt ? Wt : 1) : Wg;
-    if ((uint64_t)blockIdx.x * kRvWaves >= W) return;  // uniform per block: no share, no tail
     auto stored_crc = [&](uint64_t g) { return a.page_crcs[g + vz]; };
-    // static shares of the first Ts slots, then dynamic chunks of kRvDynSlots
-    // slots (the page kernel's tail: the XCDs run at different rates)
-    const uint64_t Ts = T - T / kRvDynDiv;
-    uint32_t dyn_head, dyn_tried;
-    tail_cursor<kRvHeads>(dyn_head, dyn_tried);
-    uint64_t lo_slot = w < W ? Ts * w / W : Ts, hi_slot = w < W ? Ts * (w + 1) / W : Ts;  // waves past W: tail only
+    auto entry = [&](uint64_t i) -> RvEntry {
+        const RangeDesc r = a.reads[i + vz];
+        return {read_pages(a, r), r.off >> a.page_shift};  // 0 pages also for reads past the pool
+    };
 #pragma unroll 1
-    for (;;) {
-        // slots [lo_slot, hi_slot) at PAGE granularity: from the read holding
-        // slot lo_slot through the reads starting before hi_slot, cut at both ends
-        uint64_t base = n, S = 0;  // the group's first read and the slot of its page 0
-        RangeDesc rs;              // the search's last 64 descriptors: the first group's (no second load)
-        bool have_rs = false;
-        if (lo_slot < hi_slot) {
-            const TileHit th = tile_of(cum, tb, lo_slot, lane);
-            base = n * th.tile / kReadTiles;
-            S = th.before;
-            // the tile's reads 64 at a time, to the group whose pages pass lo_slot
-            for (;;) {
-                const uint64_t ri = base + lane;
-                rs = a.reads[(ri < n ? ri : base) + vz];
-                const uint64_t c = wave_scan_incl(ri < n ? read_pages(a, rs) : 0u, lane);
-                const uint64_t tot = readlane64(c, 63);
-                if (S + tot > lo_slot || base + 64 >= n) break;
-                S += tot;
-                base += 64;
-            }
-            have_rs = true;
-        }
-        for (; base < n && S < hi_slot; base += 64) {
-            const uint64_t ri = base + lane;
-            const bool valid = ri < n;
-            const RangeDesc r = have_rs ? rs : a.reads[(valid ? ri : base) + vz];
-            have_rs = false;
-            const uint32_t cnt = valid ? (uint32_t)read_pages(a, r) : 0u;  // 0 also for reads past the pool
-            const uint64_t p0 = r.off >> a.page_shift;
-            uint32_t cum32 = cnt;  // inclusive prefix sum over the lanes
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t o = __shfl_up(cum32, d, 64);
-                if (lane >= (uint32_t)d) cum32 += o;
-            }
-            const uint32_t P = __builtin_amdgcn_readlane(cum32, 63);
-            const uint32_t ks = lo_slot > S ? (uint32_t)(lo_slot - S) : 0u;
-            const uint32_t ke = hi_slot - S < (uint64_t)P ? (uint32_t)(hi_slot - S) : P;
-            S += P;
-            if (ks >= ke) continue;
+    do {
+        rv_walk(sh, n, lane, entry, [&](uint64_t base, uint32_t cum32, uint64_t p0, uint32_t ks, uint32_t ke) {
             auto page_at = [&](uint32_t k, uint32_t& owner) -> uint64_t {
-                owner = (uint32_t)__builtin_ctzll(__ballot(cum32 > k));
-                const uint32_t before = owner ? (uint32_t)__builtin_amdgcn_readlane(cum32, owner - 1) : 0u;
-                const uint64_t first = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((uint32_t)(p0 >> 32), owner) << 32) |
-                                       (uint32_t)__builtin_amdgcn_readlane((uint32_t)p0, owner);
-                return first + (k - before);
+                const RvSlot s = slot_at(cum32, p0, k);
+                owner = s.owner;
+                return s.g;
             };
             uint32_t A[M], B[M], Cq[M];
             uint32_t oA, oB, oC;
@@ -2250,59 +2358,37 @@ __global__ __launch_bounds__(64 * kRvWaves) void read_verify_kernel(ReadVerifyLa
                 if (!step(B, sB, oB, k + 1, A, gA, sA, oA)) break;
                 if (!step(Cq, sC, oC, k + 2, B, gB, sB, oB)) break;
             }
-        }
-        const uint64_t n_dyn = (T - Ts + kRvDynSlots - 1) / kRvDynSlots;
-        const uint64_t c = tail_pull<kRvHeads>(dyn_ctr, n_dyn, dyn_head, dyn_tried, lane);
-        if (c >= n_dyn) break;
-        lo_slot = Ts + c * kRvDynSlots;
-        hi_slot = lo_slot + kRvDynSlots < T ? lo_slot + kRvDynSlots : T;
-    }
+        });
+    } while (rv_next(sh, lane));
 }
 
 
 // A small batch (<= 64 reads: one per lane) in ONE launch, for the per-request
-// latency of the read path: no count kernel and no scan.  Every wave loads the
-// batch's descriptors, computes the pages per read (a read past the pool is
-// marked as read_counts_kernel marks it) and their wave prefix sum; the P pages
-// are split evenly over the fewest waves that give each >= kRvMinSlots, at
-// PAGE granularity (a 32-page read is verified by 4 waves), and the blocks left
-// without pages exit before filling LDS.
+// latency of the read path: no count kernel and no scan (rv_small_begin; a
+// 32-page read is verified by 4 waves).  A wave hashes one page with the next
+// page's loads in flight.
 template <int M>
 __global__ __launch_bounds__(64 * kRvWaves) void read_verify_small_kernel(ReadVerifyLaunch a) {
     __shared__ uint32_t tab[kLdsBytes / 4];
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     uint32_t vz = 0;
     asm volatile("" : "+v"(vz));
-    const bool valid = lane < a.n_reads;
-    const RangeDesc r = a.reads[(valid ? lane : 0u) + vz];
-    const bool past = r.off >= a.pool_bytes || r.len > a.pool_bytes - r.off;
-    uint32_t cnt = 0;
-    if (valid && !past && r.len) cnt = (uint32_t)((r.off + r.len - 1) / a.page_bytes - r.off / a.page_bytes + 1);
-    if (valid && past && r.len && blockIdx.x == 0 && wave == 0) a.bad_per_read[lane] = 0xFFFFFFFFu;
-    const uint64_t p0 = r.off / a.page_bytes;
-    uint32_t cum = cnt;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = __shfl_up(cum, d, 64);
-        if (lane >= (uint32_t)d) cum += o;
-    }
-    const uint32_t P = __builtin_amdgcn_readlane(cum, 63);
-    const uint32_t Wg = gridDim.x * kRvWaves, Wt = (P + kRvSmallMinSlots - 1) / kRvSmallMinSlots;
-    const uint32_t W = Wt < Wg ? Wt : Wg;
-    if (blockIdx.x * (uint32_t)kRvWaves >= W) return;  // uniform per block (P == 0: every block)
-    fill_lds<64 * kRvWaves>(tab, static_cast<const uint4*>(a.image));
-    const uint32_t w = blockIdx.x * kRvWaves + wave;
-    if (w >= W) return;
-    const uint32_t k0 = (uint32_t)((uint64_t)P * w / W), k1 = (uint32_t)((uint64_t)P * (w + 1) / W);
+    RvSmallShare sm;
+    if (!rv_small_begin(sm, tab, a, lane, [&](uint32_t i, bool mark) -> RvEntry {
+            const RangeDesc r = a.reads[i + vz];
+            if (mark && r.len && (r.off >= a.pool_bytes || r.len > a.pool_bytes - r.off)) a.bad_per_read[i] = 0xFFFFFFFFu;
+            return {read_pages(a, r), r.off >> a.page_shift};
+        }))
+        return;
+    const uint32_t k0 = sm.k0, k1 = sm.k1;
     const uint32_t c0 = lane << 2 & 0x7Cu;
     const uint32_t c1 = c0 | 0x10000u;
     const uint32_t cf = kFinBase + (lane << 2);
     const uint32_t* pages = a.pool + lane;
     auto page_at = [&](uint32_t k, uint32_t& owner) -> uint64_t {
-        owner = (uint32_t)__builtin_ctzll(__ballot(cum > k));
-        const uint32_t before = owner ? (uint32_t)__builtin_amdgcn_readlane(cum, owner - 1) : 0u;
-        return readlane64(p0, owner) + (k - before);
+        const RvSlot s = slot_at(sm.cum, sm.p0, k);
+        owner = s.owner;
+        return s.g;
     };
     // pages k0 .. k1-1, the next page's loads in flight while one is hashed
     uint32_t X[M], Y[M];
@@ -2375,10 +2461,7 @@ __device__ __forceinline__ uint64_t snap_tile_count(const SnapReadLaunch& a, uin
 // LDS lookups) and stay in a VGPR, the same value in every lane, until the
 // next stage takes them with a readfirstlane a step later -- the wait sits
 // there, a whole page's hash after the load, not at the load.
-struct SnapPg {
-    uint64_t g;      // pool page
-    uint32_t owner;  // lane holding the page's read
-    uint32_t rel;    // the page's position in its read
+struct SnapPg : RvSlot {  // owner: lane holding the page's read; rel: the page's position in it; g: pool page
     uint32_t q;      // page in chunk
     uint32_t s;      // the chunk's slot (>= n_slots: none), once snap_word_of has taken it
     uint32_t sv;     // VGPR: the slot as loaded
@@ -2432,103 +2515,41 @@ __device__ __forceinline__ void store_page(const uint32_t (&w)[M], uint32_t* p) 
     for (int j = 0; j < M; j++) __builtin_nontemporal_store(w[j], p + 64 * j);
 }
 
-// read_verify_kernel's schedule (tile counts published by the waves, shares at
-// page granularity, 1/16 dynamic tail, three register sets rotating) with the
-// per-page source resolution: the step that hashes page k first takes the
-// table words loaded a step earlier, issues page k+3's bitmap-word load and
-// page k+4's slot load, and then page k+2's loads from the source just
-// resolved.  The table loads go BEFORE the page's: vmcnt retires in order, so a
-// table word issued after a page's loads would hold the step that needs it
-// until that page had landed, a page early.  Lane j of a group of 64 reads
-// also holds its read's output offset; a page's output address is the owner
-// lane's offset (readlane) plus its position in the read.
+// Three register sets rotating, with the per-page source resolution: the step
+// that hashes page k first takes the table words loaded a step earlier, issues
+// page k+3's bitmap-word load and page k+4's slot load, and then page k+2's
+// loads from the source just resolved.  The table loads go BEFORE the page's:
+// vmcnt retires in order, so a table word issued after a page's loads would
+// hold the step that needs it until that page had landed, a page early.  Lane
+// j of a group of 64 reads also holds its read's output offset; a page's
+// output address is the owner lane's offset (readlane) plus its position in
+// the read.
 template <int M, bool Copy>
 __global__ __launch_bounds__(64 * kRvWaves) void snap_read_kernel(SnapReadLaunch a) {
     __shared__ uint32_t tab[kLdsBytes / 4];
     const uint64_t n = a.rv.n_reads;
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint64_t Wg = (uint64_t)gridDim.x * kRvWaves;
-    const uint64_t w = (uint64_t)blockIdx.x * kRvWaves + wave;
-    const uint64_t tag = (uint64_t)a.rv.epoch << kEpochShift;
-    for (uint64_t t = w; t < kReadTiles; t += Wg) {
-        const uint64_t cnt = snap_tile_count<Copy>(a, (uint32_t)t, lane, true);
-        if (lane == 0) __hip_atomic_store(a.rv.tiles + t, tag | cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    unsigned long long* dyn_ctr = a.rv.tail + (a.rv.epoch & 1u) * kDynCtrWords64;
-    if (blockIdx.x == 0 && threadIdx.x < kRvHeads)
-        atomicExch(a.rv.tail + ((a.rv.epoch + 1u) & 1u) * kDynCtrWords64 + threadIdx.x * kDynHeadStride, 0ull);
-    fill_lds<64 * kRvWaves>(tab, static_cast<const uint4*>(a.rv.image));
+    RvShares sh;
+    if (!rv_begin(sh, tab, a.rv.tiles, a.rv.tail, a.rv.epoch, a.rv.image, lane,
+                  [&](uint32_t t, bool mark) { return snap_tile_count<Copy>(a, t, lane, mark); }))
+        return;
     const uint32_t c0 = lane << 2 & 0x7Cu;
     const uint32_t c1 = c0 | 0x10000u;
     const uint32_t cf = kFinBase + (lane << 2);
     uint32_t vz = 0;
     asm volatile("" : "+v"(vz));  // opaque zero: keeps uniform-address loads on the vector path
-
-    constexpr int kTpl = kReadTiles / 64;
-    uint64_t tb[kTpl];
-    wait_tiles<kTpl>(tb, a.rv.tiles, tag, lane, [&](uint32_t t) { return snap_tile_count<Copy>(a, t, lane, false); });
-    uint64_t lsum = 0;
-#pragma unroll
-    for (int j = 0; j < kTpl; j++) lsum += tb[j];
-    const uint64_t cum = wave_scan_incl(lsum, lane);
-    const uint64_t T = readlane64(cum, 63);
-    const uint64_t Wt = (T + kRvMinSlots - 1) / kRvMinSlots;
-    const uint64_t W = Wt < Wg ? (Wt ? Wt : 1) : Wg;
-    if ((uint64_t)blockIdx.x * kRvWaves >= W) return;  // uniform per block: no share, no tail
-    const uint64_t Ts = T - T / kRvDynDiv;
-    uint32_t dyn_head, dyn_tried;
-    tail_cursor<kRvHeads>(dyn_head, dyn_tried);
-    uint64_t lo_slot = w < W ? Ts * w / W : Ts, hi_slot = w < W ? Ts * (w + 1) / W : Ts;  // waves past W: tail only
+    uint64_t oo = 0;  // the lane's read's output offset
+    auto entry = [&](uint64_t i) -> RvEntry {
+        const RangeDesc r = a.rv.reads[i + vz];
+        oo = Copy ? a.out_off[i + vz] : 0u;
+        return {snap_pages<Copy>(a, r, oo), r.off >> a.rv.page_shift};  // 0 pages also for invalid reads
+    };
 #pragma unroll 1
-    for (;;) {
-        uint64_t base = n, S = 0;
-        RangeDesc rs;
-        uint64_t os = 0;
-        bool have_rs = false;
-        if (lo_slot < hi_slot) {
-            const TileHit th = tile_of(cum, tb, lo_slot, lane);
-            base = n * th.tile / kReadTiles;
-            S = th.before;
-            for (;;) {
-                const uint64_t ri = base + lane;
-                rs = a.rv.reads[(ri < n ? ri : base) + vz];
-                os = Copy ? a.out_off[(ri < n ? ri : base) + vz] : 0u;
-                const uint64_t c = wave_scan_incl(ri < n ? snap_pages<Copy>(a, rs, os) : 0u, lane);
-                const uint64_t tot = readlane64(c, 63);
-                if (S + tot > lo_slot || base + 64 >= n) break;
-                S += tot;
-                base += 64;
-            }
-            have_rs = true;
-        }
-        for (; base < n && S < hi_slot; base += 64) {
-            const uint64_t ri = base + lane;
-            const bool valid = ri < n;
-            const RangeDesc r = have_rs ? rs : a.rv.reads[(valid ? ri : base) + vz];
-            const uint64_t oo = !Copy ? 0u : have_rs ? os : a.out_off[(valid ? ri : base) + vz];
-            have_rs = false;
-            const uint32_t cnt = valid ? (uint32_t)snap_pages<Copy>(a, r, oo) : 0u;  // 0 also for invalid reads
-            const uint64_t p0 = r.off >> a.rv.page_shift;
-            uint32_t cum32 = cnt;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t o = __shfl_up(cum32, d, 64);
-                if (lane >= (uint32_t)d) cum32 += o;
-            }
-            const uint32_t P = __builtin_amdgcn_readlane(cum32, 63);
-            const uint32_t ks = lo_slot > S ? (uint32_t)(lo_slot - S) : 0u;
-            const uint32_t ke = hi_slot - S < (uint64_t)P ? (uint32_t)(hi_slot - S) : P;
-            S += P;
-            if (ks >= ke) continue;
+    do {
+        rv_walk(sh, n, lane, entry, [&](uint64_t base, uint32_t cum32, uint64_t p0, uint32_t ks, uint32_t ke) {
             // slot k (clamped to the share's last): its read's lane, its page, its source's chunk slot
             auto locate = [&](uint32_t k) {
-                k = k < ke ? k : ke - 1;
-                SnapPg p;
-                p.owner = (uint32_t)__builtin_ctzll(__ballot(cum32 > k));
-                const uint32_t before = p.owner ? (uint32_t)__builtin_amdgcn_readlane(cum32, p.owner - 1) : 0u;
-                p.rel = k - before;
-                p.g = readlane64(p0, p.owner) + p.rel;
+                SnapPg p = {slot_at(cum32, p0, k < ke ? k : ke - 1)};
                 snap_slot_of(a, p, vz);
                 return p;
             };
@@ -2573,59 +2594,34 @@ __global__ __launch_bounds__(64 * kRvWaves) void snap_read_kernel(SnapReadLaunch
                 if (!step(B, sB, oB, dB, k + 1, A, sA, oA, dA)) break;
                 if (!step(Cq, sC, oC, dC, k + 2, B, sB, oB, dB)) break;
             }
-        }
-        const uint64_t n_dyn = (T - Ts + kRvDynSlots - 1) / kRvDynSlots;
-        const uint64_t c = tail_pull<kRvHeads>(dyn_ctr, n_dyn, dyn_head, dyn_tried, lane);
-        if (c >= n_dyn) break;
-        lo_slot = Ts + c * kRvDynSlots;
-        hi_slot = lo_slot + kRvDynSlots < T ? lo_slot + kRvDynSlots : T;
-    }
+        });
+    } while (rv_next(sh, lane));
 }
 
-// <= 64 reads (one per lane) in ONE launch with no scratch, as
-// read_verify_small_kernel: every wave works out the batch's pages per read
-// (wave 0 of block 0 marks the invalid ones), the P pages are split evenly over
-// the fewest waves that give each >= kRvSmallMinSlots, and a wave resolves the
-// next page's source while it hashes one.
+// <= 64 reads (one per lane) in ONE launch (rv_small_begin): a wave resolves
+// the next page's source while it hashes one.
 template <int M, bool Copy>
 __global__ __launch_bounds__(64 * kRvWaves) void snap_read_small_kernel(SnapReadLaunch a) {
     __shared__ uint32_t tab[kLdsBytes / 4];
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     uint32_t vz = 0;
     asm volatile("" : "+v"(vz));
-    const bool valid = lane < a.rv.n_reads;
-    const RangeDesc r = a.rv.reads[(valid ? lane : 0u) + vz];
-    const uint64_t oo = Copy ? a.out_off[(valid ? lane : 0u) + vz] : 0u;
-    const bool bad = snap_read_bad<Copy>(a, r, oo);
-    const uint32_t cnt = valid && !bad ? (uint32_t)read_pages(a.rv, r) : 0u;
-    if (valid && bad && blockIdx.x == 0 && wave == 0) a.rv.bad_per_read[lane] = 0xFFFFFFFFu;
-    const uint64_t p0 = r.off >> a.rv.page_shift;
-    uint32_t cum = cnt;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = __shfl_up(cum, d, 64);
-        if (lane >= (uint32_t)d) cum += o;
-    }
-    const uint32_t P = __builtin_amdgcn_readlane(cum, 63);
-    const uint32_t Wg = gridDim.x * kRvWaves, Wt = (P + kRvSmallMinSlots - 1) / kRvSmallMinSlots;
-    const uint32_t W = Wt < Wg ? Wt : Wg;
-    if (blockIdx.x * (uint32_t)kRvWaves >= W) return;  // uniform per block (P == 0: every block)
-    fill_lds<64 * kRvWaves>(tab, static_cast<const uint4*>(a.rv.image));
-    const uint32_t w = blockIdx.x * kRvWaves + wave;
-    if (w >= W) return;
-    const uint32_t k0 = (uint32_t)((uint64_t)P * w / W), k1 = (uint32_t)((uint64_t)P * (w + 1) / W);
-    if (k0 >= k1) return;
+    uint64_t oo = 0;  // the lane's read's output offset
+    RvSmallShare sm;
+    if (!rv_small_begin(sm, tab, a.rv, lane, [&](uint32_t i, bool mark) -> RvEntry {
+            const RangeDesc r = a.rv.reads[i + vz];
+            oo = Copy ? a.out_off[i + vz] : 0u;
+            const bool bad = snap_read_bad<Copy>(a, r, oo);
+            if (mark && bad) a.rv.bad_per_read[i] = 0xFFFFFFFFu;
+            return {bad ? 0u : read_pages(a.rv, r), r.off >> a.rv.page_shift};
+        }))
+        return;
+    const uint32_t k0 = sm.k0, k1 = sm.k1;
     const uint32_t c0 = lane << 2 & 0x7Cu;
     const uint32_t c1 = c0 | 0x10000u;
     const uint32_t cf = kFinBase + (lane << 2);
     auto locate = [&](uint32_t k) {
-        k = k < k1 ? k : k1 - 1;
-        SnapPg p;
-        p.owner = (uint32_t)__builtin_ctzll(__ballot(cum > k));
-        const uint32_t before = p.owner ? (uint32_t)__builtin_amdgcn_readlane(cum, p.owner - 1) : 0u;
-        p.rel = k - before;
-        p.g = readlane64(p0, p.owner) + p.rel;
+        SnapPg p = {slot_at(sm.cum, sm.p0, k < k1 ? k : k1 - 1)};
         snap_slot_of(a, p, vz);
         snap_word_of(a, p, vz);
         return p;
@@ -2763,10 +2759,7 @@ __device__ __forceinline__ uint64_t paste_tile_count(const PasteLaunch& a, uint3
 // claim word), and the comparison with the slot's own entry index.  Both table
 // words come in with vector loads of a uniform address and stay in a VGPR until
 // the next stage takes them a step later.
-struct PastePg {
-    uint64_t g;      // pool page
-    uint32_t owner;  // lane holding the page's entry
-    uint32_t rel;    // the page's position in its entry
+struct PastePg : RvSlot {  // owner: lane holding the page's entry; rel: the page's position in it; g: pool page
     uint32_t q;      // page in chunk
     uint32_t s;      // the chunk's bitmap slot (>= n_slots: not a clone), once paste_claim_of has taken it
     uint32_t sv;     // VGPR: the slot as loaded
@@ -2791,9 +2784,8 @@ struct PasteDst {
     bool win;
 };
 
-// Launch 2 of cc_paste_dev, on read_verify_kernel's schedule (tile counts
-// published by the waves, shares at slot granularity, 1/16 dynamic tail, three
-// register sets rotating) over the batch's (entry, page) slots.  The slot whose
+// Launch 2 of cc_paste_dev, over the batch's (entry, page) slots, three
+// register sets rotating.  The slot whose
 // claim word equals its own entry index is the page's winner: its source page is
 // loaded two steps ahead, hashed as it passes through the registers, stored to
 // the pool, and the lane-0 epilogue writes the CRC, ORs the bit, counts and puts
@@ -2806,87 +2798,28 @@ __global__ __launch_bounds__(64 * kRvWaves) void paste_kernel(PasteLaunch a) {
     __shared__ uint32_t tab[kLdsBytes / 4];
     const uint64_t n = a.n;
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint64_t Wg = (uint64_t)gridDim.x * kRvWaves;
-    const uint64_t w = (uint64_t)blockIdx.x * kRvWaves + wave;
-    const uint64_t tag = (uint64_t)a.epoch << kEpochShift;
-    for (uint64_t t = w; t < kReadTiles; t += Wg) {
-        const uint64_t cnt = paste_tile_count(a, (uint32_t)t, lane);
-        if (lane == 0) __hip_atomic_store(a.tiles + t, tag | cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    unsigned long long* dyn_ctr = a.tail + (a.epoch & 1u) * kDynCtrWords64;
-    if (blockIdx.x == 0 && threadIdx.x < kRvHeads)
-        atomicExch(a.tail + ((a.epoch + 1u) & 1u) * kDynCtrWords64 + threadIdx.x * kDynHeadStride, 0ull);
-    fill_lds<64 * kRvWaves>(tab, static_cast<const uint4*>(a.image));
+    RvShares sh;
+    if (!rv_begin(sh, tab, a.tiles, a.tail, a.epoch, a.image, lane,
+                  [&](uint32_t t, bool) { return paste_tile_count(a, t, lane); }))
+        return;
     const uint32_t c0 = lane << 2 & 0x7Cu;
     const uint32_t c1 = c0 | 0x10000u;
     const uint32_t cf = kFinBase + (lane << 2);
     uint32_t vz = 0;
     asm volatile("" : "+v"(vz));  // opaque zero: keeps uniform-address loads on the vector path
-
-    constexpr int kTpl = kReadTiles / 64;
-    uint64_t tb[kTpl];
-    wait_tiles<kTpl>(tb, a.tiles, tag, lane, [&](uint32_t t) { return paste_tile_count(a, t, lane); });
-    uint64_t lsum = 0;
-#pragma unroll
-    for (int j = 0; j < kTpl; j++) lsum += tb[j];
-    const uint64_t cum = wave_scan_incl(lsum, lane);
-    const uint64_t T = readlane64(cum, 63);
-    const uint64_t Wt = (T + kRvMinSlots - 1) / kRvMinSlots;
-    const uint64_t W = Wt < Wg ? (Wt ? Wt : 1) : Wg;
-    if ((uint64_t)blockIdx.x * kRvWaves >= W) return;  // uniform per block: no share, no tail
-    const uint64_t Ts = T - T / kRvDynDiv;
-    uint32_t dyn_head, dyn_tried;
-    tail_cursor<kRvHeads>(dyn_head, dyn_tried);
-    uint64_t lo_slot = w < W ? Ts * w / W : Ts, hi_slot = w < W ? Ts * (w + 1) / W : Ts;  // waves past W: tail only
     uint32_t npasted = 0;  // uniform: this wave's pasted pages, added to the total once
+    uint64_t so = 0;       // the lane's entry's source offset
+    auto entry = [&](uint64_t i) -> RvEntry {
+        const UpdateDesc u = a.pastes[i + vz];
+        so = u.src;
+        return {paste_pages(a, u), u.dst >> a.page_shift};  // 0 pages also for invalid entries
+    };
 #pragma unroll 1
-    for (;;) {
-        uint64_t base = n, S = 0;
-        UpdateDesc us;
-        bool have_us = false;
-        if (lo_slot < hi_slot) {
-            const TileHit th = tile_of(cum, tb, lo_slot, lane);
-            base = n * th.tile / kReadTiles;
-            S = th.before;
-            for (;;) {
-                const uint64_t ei = base + lane;
-                us = a.pastes[(ei < n ? ei : base) + vz];
-                const uint64_t c = wave_scan_incl(ei < n ? paste_pages(a, us) : 0u, lane);
-                const uint64_t tot = readlane64(c, 63);
-                if (S + tot > lo_slot || base + 64 >= n) break;
-                S += tot;
-                base += 64;
-            }
-            have_us = true;
-        }
-        for (; base < n && S < hi_slot; base += 64) {
-            const uint64_t ei = base + lane;
-            const bool valid = ei < n;
-            const UpdateDesc u = have_us ? us : a.pastes[(valid ? ei : base) + vz];
-            have_us = false;
-            const uint32_t cnt = valid ? paste_pages(a, u) : 0u;  // 0 also for invalid entries
-            const uint64_t p0 = u.dst >> a.page_shift;
-            const uint64_t so = u.src;
-            uint32_t cum32 = cnt;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t o = __shfl_up(cum32, d, 64);
-                if (lane >= (uint32_t)d) cum32 += o;
-            }
-            const uint32_t P = __builtin_amdgcn_readlane(cum32, 63);
-            const uint32_t ks = lo_slot > S ? (uint32_t)(lo_slot - S) : 0u;
-            const uint32_t ke = hi_slot - S < (uint64_t)P ? (uint32_t)(hi_slot - S) : P;
-            S += P;
-            if (ks >= ke) continue;
+    do {
+        rv_walk(sh, n, lane, entry, [&](uint64_t base, uint32_t cum32, uint64_t p0, uint32_t ks, uint32_t ke) {
             // slot k (clamped to the share's last): its entry's lane, its page, its chunk's bitmap slot
             auto locate = [&](uint32_t k) {
-                k = k < ke ? k : ke - 1;
-                PastePg p;
-                p.owner = (uint32_t)__builtin_ctzll(__ballot(cum32 > k));
-                const uint32_t before = p.owner ? (uint32_t)__builtin_amdgcn_readlane(cum32, p.owner - 1) : 0u;
-                p.rel = k - before;
-                p.g = readlane64(p0, p.owner) + p.rel;
+                PastePg p = {slot_at(cum32, p0, k < ke ? k : ke - 1)};
                 paste_slot_of(a, p, vz);
                 return p;
             };
@@ -2939,13 +2872,8 @@ __global__ __launch_bounds__(64 * kRvWaves) void paste_kernel(PasteLaunch a) {
                 if (!step(B, dB, k + 1, A, dA)) break;
                 if (!step(Cq, dC, k + 2, B, dB)) break;
             }
-        }
-        const uint64_t n_dyn = (T - Ts + kRvDynSlots - 1) / kRvDynSlots;
-        const uint64_t c = tail_pull<kRvHeads>(dyn_ctr, n_dyn, dyn_head, dyn_tried, lane);
-        if (c >= n_dyn) break;
-        lo_slot = Ts + c * kRvDynSlots;
-        hi_slot = lo_slot + kRvDynSlots < T ? lo_slot + kRvDynSlots : T;
-    }
+        });
+    } while (rv_next(sh, lane));
     if (npasted && lane == 0 && a.pasted) atomicAdd(a.pasted, (unsigned long long)npasted);
 }
 
@@ -3409,10 +3337,7 @@ __device__ __forceinline__ uint64_t merge_tile_count(const MergeReadLaunch& a, u
 // a CLEAR bit of a clone chunk sends the page away from the pool).  Both table
 // words come in with vector loads of a uniform address and stay in a VGPR until
 // the next stage takes them a step later.
-struct MergePg {
-    uint64_t g;      // pool page
-    uint32_t owner;  // lane holding the page's read
-    uint32_t rel;    // the page's position in its read
+struct MergePg : RvSlot {  // owner: lane holding the page's read; rel: the page's position in it; g: pool page
     uint32_t q;      // page in chunk
     uint32_t s;      // the chunk's bitmap slot (>= n_slots: not a clone), once merge_word_of has taken it
     uint32_t sv;     // VGPR: the slot as loaded
@@ -3480,6 +3405,11 @@ __device__ __forceinline__ void merge_run_add(const MergeReadLaunch& a, MergeRun
 // bitmap-word load and page k+4's slot load, and then page k+2's loads -- the
 // stored CRC and the pool page, the origin page, or none.  Lane j of a group
 // of 64 reads holds its read's output offset and its origin offset.
+// This kernel keeps its own copy of the slot schedule and the group walk
+// (rv_begin, rv_next and rv_walk above, written out): on the shared functions
+// its count-only path (every page never written, no origin: no page traffic
+// to hide the scalar work behind) measured 5.5 % slower, 0.290 ms against the
+// parent's 0.2743-0.2749 ms over three runs (profiles/gather_refactor_ab.txt).  A change to the schedule is made here too.
 template <int M>
 __global__ __launch_bounds__(64 * kRvWaves) void merge_read_kernel(MergeReadLaunch a) {
     __shared__ uint32_t tab[kLdsBytes / 4];
@@ -3640,55 +3570,35 @@ __global__ __launch_bounds__(64 * kRvWaves) void merge_read_kernel(MergeReadLaun
     if (run.total && lane == 0) atomicAdd(a.unwritten_total, (unsigned long long)run.total);
 }
 
-// <= 64 reads (one per lane) in ONE launch with no scratch, as
-// snap_read_small_kernel: every wave works out the batch's pages per read
-// (wave 0 of block 0 marks the invalid ones), the P pages are split evenly over
-// the fewest waves that give each >= kRvSmallMinSlots, and a wave resolves the
-// next page while it handles one.
+// <= 64 reads (one per lane) in ONE launch (rv_small_begin): a wave resolves
+// the next page while it handles one.
 template <int M>
 __global__ __launch_bounds__(64 * kRvWaves) void merge_read_small_kernel(MergeReadLaunch a) {
     __shared__ uint32_t tab[kLdsBytes / 4];
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     uint32_t vz = 0;
     asm volatile("" : "+v"(vz));
-    const bool valid = lane < a.rv.n_reads;
-    const uint32_t at = (valid ? lane : 0u) + vz;
-    const RangeDesc r = a.rv.reads[at];
-    const uint64_t oo = a.out_off[at];
-    const uint64_t go = a.origin ? a.origin_off[at] : kNoOrigin;
-    const bool bad = merge_read_bad(a, r, oo, go);
-    const uint32_t cnt = valid && !bad ? (uint32_t)read_pages(a.rv, r) : 0u;
-    if (valid && bad && blockIdx.x == 0 && wave == 0) {
-        a.rv.bad_per_read[lane] = 0xFFFFFFFFu;
-        a.unwritten_per_read[lane] = 0xFFFFFFFFu;
-    }
-    const uint64_t p0 = r.off >> a.rv.page_shift;
-    uint32_t cum = cnt;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = __shfl_up(cum, d, 64);
-        if (lane >= (uint32_t)d) cum += o;
-    }
-    const uint32_t P = __builtin_amdgcn_readlane(cum, 63);
-    const uint32_t Wg = gridDim.x * kRvWaves, Wt = (P + kRvSmallMinSlots - 1) / kRvSmallMinSlots;
-    const uint32_t W = Wt < Wg ? Wt : Wg;
-    if (blockIdx.x * (uint32_t)kRvWaves >= W) return;  // uniform per block (P == 0: every block)
-    fill_lds<64 * kRvWaves>(tab, static_cast<const uint4*>(a.rv.image));
-    const uint32_t w = blockIdx.x * kRvWaves + wave;
-    if (w >= W) return;
-    const uint32_t k0 = (uint32_t)((uint64_t)P * w / W), k1 = (uint32_t)((uint64_t)P * (w + 1) / W);
-    if (k0 >= k1) return;
+    uint64_t oo = 0, go = kNoOrigin;  // the lane's read's output and origin offsets
+    RvSmallShare sm;
+    if (!rv_small_begin(sm, tab, a.rv, lane, [&](uint32_t i, bool mark) -> RvEntry {
+            const uint32_t at = i + vz;
+            const RangeDesc r = a.rv.reads[at];
+            oo = a.out_off[at];
+            go = a.origin ? a.origin_off[at] : kNoOrigin;
+            const bool bad = merge_read_bad(a, r, oo, go);
+            if (mark && bad) {
+                a.rv.bad_per_read[i] = 0xFFFFFFFFu;
+                a.unwritten_per_read[i] = 0xFFFFFFFFu;
+            }
+            return {bad ? 0u : read_pages(a.rv, r), r.off >> a.rv.page_shift};
+        }))
+        return;
+    const uint32_t k0 = sm.k0, k1 = sm.k1;
     const uint32_t c0 = lane << 2 & 0x7Cu;
     const uint32_t c1 = c0 | 0x10000u;
     const uint32_t cf = kFinBase + (lane << 2);
     auto locate = [&](uint32_t k) {
-        k = k < k1 ? k : k1 - 1;
-        MergePg p;
-        p.owner = (uint32_t)__builtin_ctzll(__ballot(cum > k));
-        const uint32_t before = p.owner ? (uint32_t)__builtin_amdgcn_readlane(cum, p.owner - 1) : 0u;
-        p.rel = k - before;
-        p.g = readlane64(p0, p.owner) + p.rel;
+        MergePg p = {slot_at(sm.cum, sm.p0, k < k1 ? k : k1 - 1)};
         merge_slot_of(a, p, vz);
         merge_word_of(a, p, vz);
         return p;
@@ -3842,6 +3752,11 @@ __device__ __forceinline__ void repair_run_add(const RepairLaunch& a, RepairRun&
 // its own index (paste_kernel's comment), so no third launch is needed.  Only
 // the page's handler reads or writes the page and its CRC word, so every page
 // is judged by the pool as it stood before the call.
+// Like merge_read_kernel this kernel keeps its own copy of the slot schedule
+// and the group walk: on the shared functions its two rows without page
+// traffic to hide scalar work behind measured slower, every page clean 0.47 %
+// and every pair shadowed 0.62 % above the parent's range of five runs
+// (profiles/gather_refactor_ab.txt).  A change to the schedule is made here too.
 template <int M>
 __global__ __launch_bounds__(64 * kRvWaves) void repair_kernel(RepairLaunch a) {
     __shared__ uint32_t tab[kLdsBytes / 4];
@@ -4133,7 +4048,7 @@ struct ScrubPg {
     uint32_t want;  // the stored CRC
 };
 
-// read_verify_kernel's schedule with groups in the place of reads.  A wave's
+// The slot schedule with groups in the place of entries.  A wave's
 // share is [lo, hi) of the present pages in domain order: the tile search in
 // registers, then the tile's groups 64 at a time (a lane counts one group from
 // the bitmap words) to the group holding page lo.  From there one lane
@@ -4142,52 +4057,32 @@ struct ScrubPg {
 // ballot of the present lanes is the group's page list, walked with scalar
 // math across group boundaries so three register sets keep rotating for the
 // whole share.  The three counts a scrub owes for pages it never hashes leave
-// with the tile counts (each tile's own wave counts it once: one atomic a
-// count a wave); a mismatch costs its atomics on the spot.
+// with the tile counts: each tile's own wave counts it once and adds the
+// tile's counts with one atomic each.  With gridDim.x * kRvWaves >= kReadTiles
+// (one workgroup a CU on 64 CUs or more: the MI355X has 256) a wave counts at
+// most one tile, so that is one atomic a count a wave; a smaller grid pays up
+// to three atomics for every further tile of a wave, with the same sums.  A
+// mismatch costs its atomics on the spot.
 template <int M>
 __global__ __launch_bounds__(64 * kRvWaves) void scrub_kernel(ScrubLaunch a) {
     __shared__ uint32_t tab[kLdsBytes / 4];
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint64_t Wg = (uint64_t)gridDim.x * kRvWaves;
-    const uint64_t w = (uint64_t)blockIdx.x * kRvWaves + wave;
-    const uint64_t tag = (uint64_t)a.epoch << kEpochShift;
     const uint64_t G = a.n_groups;
-    {
-        ScrubCount mine = {0, 0, 0};
-        for (uint64_t t = w; t < kReadTiles; t += Wg) {
-            const uint64_t cnt = scrub_tile_count(a, (uint32_t)t, lane, &mine);
-            if (lane == 0) __hip_atomic_store(a.tiles + t, tag | cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        if (lane == 0) {
-            if (mine.live) atomicAdd(a.counts + 0, (unsigned long long)mine.live);
-            if (mine.snap) atomicAdd(a.counts + 2, (unsigned long long)mine.snap);
-            if (mine.unwritten) atomicAdd(a.counts + 4, (unsigned long long)mine.unwritten);
-        }
-    }
-    unsigned long long* dyn_ctr = a.tail + (a.epoch & 1u) * kDynCtrWords64;
-    if (blockIdx.x == 0 && threadIdx.x < kRvHeads)
-        atomicExch(a.tail + ((a.epoch + 1u) & 1u) * kDynCtrWords64 + threadIdx.x * kDynHeadStride, 0ull);
-    fill_lds<64 * kRvWaves>(tab, static_cast<const uint4*>(a.image));
+    RvShares sh;
+    if (!rv_begin(sh, tab, a.tiles, a.tail, a.epoch, a.image, lane, [&](uint32_t t, bool mark) {
+            ScrubCount mine = {0, 0, 0};  // the tile's three counts, owed by the tile's own wave alone
+            const uint64_t present = scrub_tile_count(a, t, lane, mark ? &mine : nullptr);
+            if (mark && lane == 0) {
+                if (mine.live) atomicAdd(a.counts + 0, (unsigned long long)mine.live);
+                if (mine.snap) atomicAdd(a.counts + 2, (unsigned long long)mine.snap);
+                if (mine.unwritten) atomicAdd(a.counts + 4, (unsigned long long)mine.unwritten);
+            }
+            return present;
+        }))
+        return;
     const uint32_t c0 = lane << 2 & 0x7Cu;
     const uint32_t c1 = c0 | 0x10000u;
     const uint32_t cf = kFinBase + (lane << 2);
-
-    constexpr int kTpl = kReadTiles / 64;
-    uint64_t tb[kTpl];
-    wait_tiles<kTpl>(tb, a.tiles, tag, lane, [&](uint32_t t) { return scrub_tile_count(a, t, lane, nullptr); });
-    uint64_t lsum = 0;
-#pragma unroll
-    for (int j = 0; j < kTpl; j++) lsum += tb[j];
-    const uint64_t cum = wave_scan_incl(lsum, lane);
-    const uint64_t T = readlane64(cum, 63);
-    const uint64_t Wt = (T + kRvMinSlots - 1) / kRvMinSlots;
-    const uint64_t W = Wt < Wg ? (Wt ? Wt : 1) : Wg;
-    if ((uint64_t)blockIdx.x * kRvWaves >= W) return;  // uniform per block: no share, no tail
-    const uint64_t Ts = T - T / kRvDynDiv;
-    uint32_t dyn_head, dyn_tried;
-    tail_cursor<kRvHeads>(dyn_head, dyn_tried);
-    uint64_t lo_slot = w < W ? Ts * w / W : Ts, hi_slot = w < W ? Ts * (w + 1) / W : Ts;  // waves past W: tail only
     uint32_t live_bad = 0, snap_bad = 0;
     // a mismatch (rare; lane 0): the list cursor, the chunk's word
     auto report = [&](const ScrubPg& p) {
@@ -4204,10 +4099,11 @@ __global__ __launch_bounds__(64 * kRvWaves) void scrub_kernel(ScrubLaunch a) {
             live_bad++;
     };
 #pragma unroll 1
-    for (;;) {
+    do {
+        const uint64_t lo_slot = sh.lo_slot, hi_slot = sh.hi_slot;
         if (lo_slot < hi_slot) {
             // the group holding present page lo_slot, and the present pages before it
-            const TileHit th = tile_of(cum, tb, lo_slot, lane);
+            const TileHit th = tile_of(sh.cum, sh.tb, lo_slot, lane);
             uint64_t g = G * th.tile / kReadTiles, S = th.before;
             for (;;) {
                 const uint64_t gi = g + lane;
@@ -4308,12 +4204,7 @@ __global__ __launch_bounds__(64 * kRvWaves) void scrub_kernel(ScrubLaunch a) {
                 }
             }
         }
-        const uint64_t n_dyn = (T - Ts + kRvDynSlots - 1) / kRvDynSlots;
-        const uint64_t c = tail_pull<kRvHeads>(dyn_ctr, n_dyn, dyn_head, dyn_tried, lane);
-        if (c >= n_dyn) break;
-        lo_slot = Ts + c * kRvDynSlots;
-        hi_slot = lo_slot + kRvDynSlots < T ? lo_slot + kRvDynSlots : T;
-    }
+    } while (rv_next(sh, lane));
     if (lane == 0) {
         if (live_bad) atomicAdd(a.counts + 1, (unsigned long long)live_bad);
         if (snap_bad) atomicAdd(a.counts + 3, (unsigned long long)snap_bad);
@@ -4340,31 +4231,40 @@ TailExtra tail_extra(const PageLaunch& a) {
             a.dyn_ctr ? a.dyn_next : nullptr};
 }
 
+// The kernels are instantiated for M = page_bytes / 256 in 1, 2, 4, ..., 32:
+// launch(std::integral_constant<int, M>) for the one that matches, and the
+// launch's error; hipErrorInvalidValue for any other page size.
+template <typename Launch>
+hipError_t for_page_words(uint32_t m, Launch launch) {
+    switch (m) {
+        case 1: launch(std::integral_constant<int, 1>()); break;
+        case 2: launch(std::integral_constant<int, 2>()); break;
+        case 4: launch(std::integral_constant<int, 4>()); break;
+        case 8: launch(std::integral_constant<int, 8>()); break;
+        case 16: launch(std::integral_constant<int, 16>()); break;
+        case 32: launch(std::integral_constant<int, 32>()); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
 template <int MODE>
 hipError_t launch_page(const PageLaunch& a, hipStream_t s) {
     const dim3 grid(a.blocks), block(kBlockThreads);
     const uint4* img = static_cast<const uint4*>(a.image);
     const ZeroRanges zr = {{a.zero[0], a.zero[1]}, {a.zero[0] ? a.zero_words[0] : 0, a.zero[1] ? a.zero_words[1] : 0}};
     const TailExtra ex = tail_extra(a);
-#define CC_CASE(MM)                                                                                     \
-    case MM:                                                                                            \
-        hipExtLaunchKernelGGL((page_crc_kernel<MM, MODE>), grid, block, 0, s, a.ev_begin, a.ev_end, 0u,  \
-                              a.pages, a.n_pages, img, a.kconst, a.out, a.expected, a.sink, a.tile_shift, \
-                              a.dyn_ctr, a.static_tiles, zr, ex);                                       \
-        break;
-    switch (a.words_per_lane) {
-        CC_CASE(1)
-        CC_CASE(2)
-        CC_CASE(4)
-        CC_CASE(8)
-        CC_CASE(16)
-        CC_CASE(32)
-        default:
-            hipExtLaunchKernelGGL((page_crc_kernel_dyn<MODE>), grid, block, 0, s, a.ev_begin, a.ev_end, 0u, a.pages,
-                                  a.n_pages, a.words_per_lane, img, a.kconst, a.out, a.expected, a.sink, zr);
+    const uint32_t m = a.words_per_lane;
+    if (m == 0 || m > 32 || (m & (m - 1))) {  // no instantiation for this page size: the any-size kernel
+        hipExtLaunchKernelGGL((page_crc_kernel_dyn<MODE>), grid, block, 0, s, a.ev_begin, a.ev_end, 0u, a.pages,
+                              a.n_pages, m, img, a.kconst, a.out, a.expected, a.sink, zr);
+        return hipGetLastError();
     }
-#undef CC_CASE
-    return hipGetLastError();
+    return for_page_words(m, [&](auto mm) {
+        hipExtLaunchKernelGGL((page_crc_kernel<decltype(mm)::value, MODE>), grid, block, 0, s, a.ev_begin, a.ev_end, 0u,
+                              a.pages, a.n_pages, img, a.kconst, a.out, a.expected, a.sink, a.tile_shift, a.dyn_ctr,
+                              a.static_tiles, zr, ex);
+    });
 }
 
 }  // namespace
@@ -4465,72 +4365,37 @@ hipError_t launch_log_insert(const LogLaunch& a, hipStream_t s) {
 
 hipError_t launch_log_pages(const LogLaunch& a, hipStream_t s) {
     if (a.n_pieces == 0) return hipSuccess;
-#define CC_GCASE(MM)                                                                                        \
-    case MM:                                                                                                \
-        if (a.delta)                                                                                        \
-            hipLaunchKernelGGL((log_pages_kernel<MM, true>), dim3(a.blocks), dim3(64 * log_waves(MM, true)), 0, s,  \
-                               a);                                                                          \
-        else                                                                                                \
-            hipLaunchKernelGGL((log_pages_kernel<MM, false>), dim3(a.blocks), dim3(64 * log_waves(MM, false)), 0, \
-                               s, a);                                                                       \
-        break;
-    switch (a.page_bytes / kWaveBytes) {
-        CC_GCASE(1)
-        CC_GCASE(2)
-        CC_GCASE(4)
-        CC_GCASE(8)
-        CC_GCASE(16)
-        CC_GCASE(32)
-        default: return hipErrorInvalidValue;
-    }
-#undef CC_GCASE
-    return hipGetLastError();
+    return for_page_words(a.page_bytes / kWaveBytes, [&](auto m) {
+        constexpr int MM = decltype(m)::value;
+        if (a.delta)
+            hipLaunchKernelGGL((log_pages_kernel<MM, true>), dim3(a.blocks), dim3(64 * log_waves(MM, true)), 0, s, a);
+        else
+            hipLaunchKernelGGL((log_pages_kernel<MM, false>), dim3(a.blocks), dim3(64 * log_waves(MM, false)), 0, s, a);
+    });
 }
 
 hipError_t launch_log_cow(const LogCowLaunch& a, hipStream_t s) {
     if (a.n_segs == 0 || a.n_segs > kInsertBlocks || a.blocks <= 0) return hipErrorInvalidValue;
-#define CC_WCASE(MM)                                                                                          \
-    case MM:                                                                                                  \
-        if (a.stale)                                                                                          \
-            hipLaunchKernelGGL((log_cow_kernel<MM, true>), dim3(a.blocks), dim3(64 * kCowWaves), 0, s, a);    \
-        else                                                                                                  \
-            hipLaunchKernelGGL((log_cow_kernel<MM, false>), dim3(a.blocks), dim3(64 * kCowWaves), 0, s, a);   \
-        break;
-    switch (a.page_bytes / kWaveBytes) {
-        CC_WCASE(1)
-        CC_WCASE(2)
-        CC_WCASE(4)
-        CC_WCASE(8)
-        CC_WCASE(16)
-        CC_WCASE(32)
-        default: return hipErrorInvalidValue;
-    }
-#undef CC_WCASE
-    return hipGetLastError();
+    return for_page_words(a.page_bytes / kWaveBytes, [&](auto m) {
+        constexpr int MM = decltype(m)::value;
+        if (a.stale)
+            hipLaunchKernelGGL((log_cow_kernel<MM, true>), dim3(a.blocks), dim3(64 * kCowWaves), 0, s, a);
+        else
+            hipLaunchKernelGGL((log_cow_kernel<MM, false>), dim3(a.blocks), dim3(64 * kCowWaves), 0, s, a);
+    });
 }
 
 hipError_t launch_log_small(const LogLaunch& a, hipStream_t s) {
     if (a.n_updates == 0 || a.n_updates > 64 || a.slots > 2) return hipErrorInvalidValue;
-#define CC_SMCASE(MM)                                                                                         \
-    case MM:                                                                                                  \
-        if (a.delta)                                                                                          \
-            hipLaunchKernelGGL((log_small_kernel<MM, true>), dim3(a.blocks), dim3(64 * log_small_waves(MM, true)), 0, s, \
-                               a);                                                                            \
-        else                                                                                                  \
-            hipLaunchKernelGGL((log_small_kernel<MM, false>), dim3(a.blocks), dim3(64 * log_small_waves(MM, false)), 0, \
-                               s, a);                                                                         \
-        break;
-    switch (a.page_bytes / kWaveBytes) {
-        CC_SMCASE(1)
-        CC_SMCASE(2)
-        CC_SMCASE(4)
-        CC_SMCASE(8)
-        CC_SMCASE(16)
-        CC_SMCASE(32)
-        default: return hipErrorInvalidValue;
-    }
-#undef CC_SMCASE
-    return hipGetLastError();
+    return for_page_words(a.page_bytes / kWaveBytes, [&](auto m) {
+        constexpr int MM = decltype(m)::value;
+        if (a.delta)
+            hipLaunchKernelGGL((log_small_kernel<MM, true>), dim3(a.blocks), dim3(64 * log_small_waves(MM, true)), 0, s,
+                               a);
+        else
+            hipLaunchKernelGGL((log_small_kernel<MM, false>), dim3(a.blocks), dim3(64 * log_small_waves(MM, false)), 0,
+                               s, a);
+    });
 }
 
 
@@ -4548,80 +4413,38 @@ hipError_t launch_log_probe(const LogProbeLaunch& a, hipStream_t s) {
 
 hipError_t launch_read_verify_small(const ReadVerifyLaunch& a, hipStream_t s) {
     if (a.n_reads == 0 || a.n_reads > 64) return hipErrorInvalidValue;
-#define CC_SCASE(MM) \
-    case MM: hipLaunchKernelGGL((read_verify_small_kernel<MM>), dim3(a.blocks), dim3(64 * kRvWaves), 0, s, a); break;
-    switch (a.page_bytes / kWaveBytes) {
-        CC_SCASE(1)
-        CC_SCASE(2)
-        CC_SCASE(4)
-        CC_SCASE(8)
-        CC_SCASE(16)
-        CC_SCASE(32)
-        default: return hipErrorInvalidValue;
-    }
-#undef CC_SCASE
-    return hipGetLastError();
+    return for_page_words(a.page_bytes / kWaveBytes, [&](auto m) {
+        hipLaunchKernelGGL((read_verify_small_kernel<decltype(m)::value>), dim3(a.blocks), dim3(64 * kRvWaves), 0, s, a);
+    });
 }
 
 hipError_t launch_read_verify(const ReadVerifyLaunch& a, hipStream_t s) {
     if (a.n_reads == 0) return hipSuccess;
-#define CC_RCASE(MM) \
-    case MM: hipLaunchKernelGGL((read_verify_kernel<MM>), dim3(a.blocks), dim3(64 * kRvWaves), 0, s, a); break;
-    switch (a.page_bytes / kWaveBytes) {
-        CC_RCASE(1)
-        CC_RCASE(2)
-        CC_RCASE(4)
-        CC_RCASE(8)
-        CC_RCASE(16)
-        CC_RCASE(32)
-        default: return hipErrorInvalidValue;
-    }
-#undef CC_RCASE
-    return hipGetLastError();
+    return for_page_words(a.page_bytes / kWaveBytes, [&](auto m) {
+        hipLaunchKernelGGL((read_verify_kernel<decltype(m)::value>), dim3(a.blocks), dim3(64 * kRvWaves), 0, s, a);
+    });
 }
 
 hipError_t launch_snap_read_small(const SnapReadLaunch& a, hipStream_t s) {
     if (a.rv.n_reads == 0 || a.rv.n_reads > 64) return hipErrorInvalidValue;
-#define CC_SCASE(MM)                                                                                                  \
-    case MM:                                                                                                          \
-        if (a.out)                                                                                                    \
-            hipLaunchKernelGGL((snap_read_small_kernel<MM, true>), dim3(a.rv.blocks), dim3(64 * kRvWaves), 0, s, a);  \
-        else                                                                                                          \
-            hipLaunchKernelGGL((snap_read_small_kernel<MM, false>), dim3(a.rv.blocks), dim3(64 * kRvWaves), 0, s, a); \
-        break;
-    switch (a.rv.page_bytes / kWaveBytes) {
-        CC_SCASE(1)
-        CC_SCASE(2)
-        CC_SCASE(4)
-        CC_SCASE(8)
-        CC_SCASE(16)
-        CC_SCASE(32)
-        default: return hipErrorInvalidValue;
-    }
-#undef CC_SCASE
-    return hipGetLastError();
+    return for_page_words(a.rv.page_bytes / kWaveBytes, [&](auto m) {
+        constexpr int MM = decltype(m)::value;
+        if (a.out)
+            hipLaunchKernelGGL((snap_read_small_kernel<MM, true>), dim3(a.rv.blocks), dim3(64 * kRvWaves), 0, s, a);
+        else
+            hipLaunchKernelGGL((snap_read_small_kernel<MM, false>), dim3(a.rv.blocks), dim3(64 * kRvWaves), 0, s, a);
+    });
 }
 
 hipError_t launch_snap_read(const SnapReadLaunch& a, hipStream_t s) {
     if (a.rv.n_reads == 0) return hipSuccess;
-#define CC_RCASE(MM)                                                                                            \
-    case MM:                                                                                                    \
-        if (a.out)                                                                                              \
-            hipLaunchKernelGGL((snap_read_kernel<MM, true>), dim3(a.rv.blocks), dim3(64 * kRvWaves), 0, s, a);  \
-        else                                                                                                    \
-            hipLaunchKernelGGL((snap_read_kernel<MM, false>), dim3(a.rv.blocks), dim3(64 * kRvWaves), 0, s, a); \
-        break;
-    switch (a.rv.page_bytes / kWaveBytes) {
-        CC_RCASE(1)
-        CC_RCASE(2)
-        CC_RCASE(4)
-        CC_RCASE(8)
-        CC_RCASE(16)
-        CC_RCASE(32)
-        default: return hipErrorInvalidValue;
-    }
-#undef CC_RCASE
-    return hipGetLastError();
+    return for_page_words(a.rv.page_bytes / kWaveBytes, [&](auto m) {
+        constexpr int MM = decltype(m)::value;
+        if (a.out)
+            hipLaunchKernelGGL((snap_read_kernel<MM, true>), dim3(a.rv.blocks), dim3(64 * kRvWaves), 0, s, a);
+        else
+            hipLaunchKernelGGL((snap_read_kernel<MM, false>), dim3(a.rv.blocks), dim3(64 * kRvWaves), 0, s, a);
+    });
 }
 
 // a wave per 64 entries, up to 8 workgroups a CU
@@ -4638,21 +4461,9 @@ hipError_t launch_paste_claim(const PasteLaunch& a, hipStream_t s) {
 
 hipError_t launch_paste(const PasteLaunch& a, hipStream_t s) {
     if (a.n == 0 || a.geo.n_slots == 0) return hipSuccess;
-#define CC_PCASE(MM)                                                                              \
-    case MM:                                                                                      \
-        hipLaunchKernelGGL((paste_kernel<MM>), dim3(a.blocks), dim3(64 * kRvWaves), 0, s, a);     \
-        break;
-    switch (a.page_bytes / kWaveBytes) {
-        CC_PCASE(1)
-        CC_PCASE(2)
-        CC_PCASE(4)
-        CC_PCASE(8)
-        CC_PCASE(16)
-        CC_PCASE(32)
-        default: return hipErrorInvalidValue;
-    }
-#undef CC_PCASE
-    return hipGetLastError();
+    return for_page_words(a.page_bytes / kWaveBytes, [&](auto m) {
+        hipLaunchKernelGGL((paste_kernel<decltype(m)::value>), dim3(a.blocks), dim3(64 * kRvWaves), 0, s, a);
+    });
 }
 
 hipError_t launch_clone_mark(const CloneMarkLaunch& a, hipStream_t s) {
@@ -4667,24 +4478,13 @@ hipError_t launch_logs_prepass(const LogsPrepassLaunch& a, hipStream_t s) {
     if (a.page_bytes != 1u << a.page_shift || (a.snap_slot && a.pages_per_chunk == 0) ||
         (a.clone.clone_slot && a.clone.pages_per_chunk == 0))
         return hipErrorInvalidValue;
-#define CC_PPCASE(MM)                                                                                                \
-    case MM:                                                                                                         \
-        if (a.stale)                                                                                                 \
-            hipLaunchKernelGGL((logs_prepass_kernel<MM, true>), dim3(a.blocks), dim3(64 * kPrepassWaves), 0, s, a);  \
-        else                                                                                                         \
-            hipLaunchKernelGGL((logs_prepass_kernel<MM, false>), dim3(a.blocks), dim3(64 * kPrepassWaves), 0, s, a); \
-        break;
-    switch (a.page_bytes / kWaveBytes) {
-        CC_PPCASE(1)
-        CC_PPCASE(2)
-        CC_PPCASE(4)
-        CC_PPCASE(8)
-        CC_PPCASE(16)
-        CC_PPCASE(32)
-        default: return hipErrorInvalidValue;
-    }
-#undef CC_PPCASE
-    return hipGetLastError();
+    return for_page_words(a.page_bytes / kWaveBytes, [&](auto m) {
+        constexpr int MM = decltype(m)::value;
+        if (a.stale)
+            hipLaunchKernelGGL((logs_prepass_kernel<MM, true>), dim3(a.blocks), dim3(64 * kPrepassWaves), 0, s, a);
+        else
+            hipLaunchKernelGGL((logs_prepass_kernel<MM, false>), dim3(a.blocks), dim3(64 * kPrepassWaves), 0, s, a);
+    });
 }
 
 static bool ops_launch_ok(const OpsLaunch& a) {
@@ -4709,21 +4509,9 @@ hipError_t launch_ops_resolve(const OpsLaunch& a, hipStream_t s) {
 
 hipError_t launch_ops_paste(const OpsLaunch& a, hipStream_t s) {
     if (!ops_launch_ok(a)) return hipErrorInvalidValue;
-#define CC_OPCASE(MM)                                                                              \
-    case MM:                                                                                       \
-        hipLaunchKernelGGL((ops_paste_kernel<MM>), dim3(a.blocks), dim3(64 * kOpsWaves), 0, s, a); \
-        break;
-    switch (a.page_bytes / kWaveBytes) {
-        CC_OPCASE(1)
-        CC_OPCASE(2)
-        CC_OPCASE(4)
-        CC_OPCASE(8)
-        CC_OPCASE(16)
-        CC_OPCASE(32)
-        default: return hipErrorInvalidValue;
-    }
-#undef CC_OPCASE
-    return hipGetLastError();
+    return for_page_words(a.page_bytes / kWaveBytes, [&](auto m) {
+        hipLaunchKernelGGL((ops_paste_kernel<decltype(m)::value>), dim3(a.blocks), dim3(64 * kOpsWaves), 0, s, a);
+    });
 }
 
 hipError_t launch_clone_check(const CloneCheckLaunch& a, hipStream_t s) {
@@ -4734,40 +4522,16 @@ hipError_t launch_clone_check(const CloneCheckLaunch& a, hipStream_t s) {
 
 hipError_t launch_merge_read_small(const MergeReadLaunch& a, hipStream_t s) {
     if (a.rv.n_reads == 0 || a.rv.n_reads > 64) return hipErrorInvalidValue;
-#define CC_MCASE(MM)                                                                                         \
-    case MM:                                                                                                 \
-        hipLaunchKernelGGL((merge_read_small_kernel<MM>), dim3(a.rv.blocks), dim3(64 * kRvWaves), 0, s, a);  \
-        break;
-    switch (a.rv.page_bytes / kWaveBytes) {
-        CC_MCASE(1)
-        CC_MCASE(2)
-        CC_MCASE(4)
-        CC_MCASE(8)
-        CC_MCASE(16)
-        CC_MCASE(32)
-        default: return hipErrorInvalidValue;
-    }
-#undef CC_MCASE
-    return hipGetLastError();
+    return for_page_words(a.rv.page_bytes / kWaveBytes, [&](auto m) {
+        hipLaunchKernelGGL((merge_read_small_kernel<decltype(m)::value>), dim3(a.rv.blocks), dim3(64 * kRvWaves), 0, s, a);
+    });
 }
 
 hipError_t launch_merge_read(const MergeReadLaunch& a, hipStream_t s) {
     if (a.rv.n_reads == 0) return hipSuccess;
-#define CC_MCASE(MM)                                                                                   \
-    case MM:                                                                                           \
-        hipLaunchKernelGGL((merge_read_kernel<MM>), dim3(a.rv.blocks), dim3(64 * kRvWaves), 0, s, a);  \
-        break;
-    switch (a.rv.page_bytes / kWaveBytes) {
-        CC_MCASE(1)
-        CC_MCASE(2)
-        CC_MCASE(4)
-        CC_MCASE(8)
-        CC_MCASE(16)
-        CC_MCASE(32)
-        default: return hipErrorInvalidValue;
-    }
-#undef CC_MCASE
-    return hipGetLastError();
+    return for_page_words(a.rv.page_bytes / kWaveBytes, [&](auto m) {
+        hipLaunchKernelGGL((merge_read_kernel<decltype(m)::value>), dim3(a.rv.blocks), dim3(64 * kRvWaves), 0, s, a);
+    });
 }
 
 hipError_t launch_repair_claim(const RepairLaunch& a, hipStream_t s) {
@@ -4778,40 +4542,16 @@ hipError_t launch_repair_claim(const RepairLaunch& a, hipStream_t s) {
 
 hipError_t launch_repair(const RepairLaunch& a, hipStream_t s) {
     if (a.n == 0) return hipSuccess;
-#define CC_FCASE(MM)                                                                               \
-    case MM:                                                                                       \
-        hipLaunchKernelGGL((repair_kernel<MM>), dim3(a.blocks), dim3(64 * kRvWaves), 0, s, a);     \
-        break;
-    switch (a.page_bytes / kWaveBytes) {
-        CC_FCASE(1)
-        CC_FCASE(2)
-        CC_FCASE(4)
-        CC_FCASE(8)
-        CC_FCASE(16)
-        CC_FCASE(32)
-        default: return hipErrorInvalidValue;
-    }
-#undef CC_FCASE
-    return hipGetLastError();
+    return for_page_words(a.page_bytes / kWaveBytes, [&](auto m) {
+        hipLaunchKernelGGL((repair_kernel<decltype(m)::value>), dim3(a.blocks), dim3(64 * kRvWaves), 0, s, a);
+    });
 }
 
 hipError_t launch_scrub(const ScrubLaunch& a, hipStream_t s) {
     if (a.n_index == 0) return hipSuccess;
-#define CC_SCASE(MM)                                                                            \
-    case MM:                                                                                    \
-        hipLaunchKernelGGL((scrub_kernel<MM>), dim3(a.blocks), dim3(64 * kRvWaves), 0, s, a);   \
-        break;
-    switch (a.words_per_lane) {
-        CC_SCASE(1)
-        CC_SCASE(2)
-        CC_SCASE(4)
-        CC_SCASE(8)
-        CC_SCASE(16)
-        CC_SCASE(32)
-        default: return hipErrorInvalidValue;
-    }
-#undef CC_SCASE
-    return hipGetLastError();
+    return for_page_words(a.words_per_lane, [&](auto m) {
+        hipLaunchKernelGGL((scrub_kernel<decltype(m)::value>), dim3(a.blocks), dim3(64 * kRvWaves), 0, s, a);
+    });
 }
 
 hipError_t launch_scrub_plain(unsigned long long* counts, uint64_t n_pages, int post, hipStream_t s) {

@@ -227,6 +227,33 @@ def test_lowest_index_wins(dev, oracle):
     assert int(rig.bm[2, 0]) == 1 << 31 and int(rig.bm[2, 1]) == 0b11
 
 
+# --------------------------------------------------------------------------- schedule edges
+def pastes_with_slots(rng, total):
+    """Pastes of 1-8 pages, each from a place of its own in the source, whose page counts sum to `total` exactly."""
+    out, left = [], total
+    while left:
+        k = min(int(rng.integers(1, 9)), left)
+        out.append((int(rng.integers(0, N_PAGES - k + 1)), int(rng.integers(0, SRC_PAGES - k + 1)), k))
+        left -= k
+    return out
+
+
+@pytest.mark.parametrize("pb", [1024, 4096])
+@pytest.mark.parametrize("total", [1, 63, 64, 65, 1023])
+def test_slot_totals_at_the_schedules_edges(dev, oracle, pb, total):
+    """The paste launch's shares at its edges: one slot, one short of a group of
+    64, a whole group, one over, and a total that leaves a dynamic tail with a
+    short last chunk; every bit clear, so every first slot of a clone page pastes."""
+    rig = Rig(dev, oracle, pb, seed=7 + total, density=0.0)
+    entries = rig.entries(pastes_with_slots(np.random.default_rng(total), total))
+    assert sum(e[2] for e in entries) == total * pb
+    pasted, held, lost, plain = classes(entries, rig.slots, rig.bm, pb, rig.host.size, rig.src.size)
+    assert held == 0 and pasted + lost + plain == total
+    got, want = rig.paste(entries)
+    assert got.tolist() == want.tolist() and int(got.sum()) == pasted == rig.total
+    rig.check()
+
+
 # --------------------------------------------------------------------------- 4
 def test_invalid_entries_write_nothing(dev, oracle):
     pb = 512
