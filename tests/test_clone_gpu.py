@@ -52,10 +52,10 @@ def to_dev(a, dev):
     return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
 
 
-def random_bitmaps(rng, density):
-    bm = np.zeros((N_SLOTS, (PPC + 31) // 32), np.uint32)
+def random_bitmaps(rng, density, ppc=PPC):
+    bm = np.zeros((N_SLOTS, (ppc + 31) // 32), np.uint32)
     for s in range(N_SLOTS):
-        for q in range(PPC):
+        for q in range(ppc):
             if rng.random() < density:
                 set_bit(bm, s, q)
     return bm
@@ -71,7 +71,7 @@ def random_pastes(rng, n=200, lo=1, hi=8):
     return out
 
 
-def classes(entries, slots, bm, pb, pool_bytes, src_bytes):
+def classes(entries, slots, bm, pb, pool_bytes, src_bytes, ppc=PPC):
     """The (entry, page) slots of a batch by what becomes of them, from the bitmaps BEFORE the call:
     (pasted, bit already set, lost to an earlier entry, chunk is no clone)."""
     pasted = held = lost = plain = 0
@@ -80,7 +80,7 @@ def classes(entries, slots, bm, pb, pool_bytes, src_bytes):
         if not paste_valid(dst, so, ln, pool_bytes, src_bytes, pb):
             continue
         for p in range(dst // pb, (dst + ln) // pb):
-            c, q = divmod(p, PPC)
+            c, q = divmod(p, ppc)
             s = int(slots[c])
             if s >= N_SLOTS:
                 plain += 1
@@ -97,10 +97,10 @@ def classes(entries, slots, bm, pb, pool_bytes, src_bytes):
 class Rig:
     """A pool with clone chunks on the device and its host mirror, advanced together one call at a time."""
 
-    def __init__(self, dev, oracle, pb, seed=1, density=0.3, stream=None):
+    def __init__(self, dev, oracle, pb, seed=1, density=0.3, stream=None, ppc=PPC, src_pages=SRC_PAGES):
         from curve_amd import crc as C
         self.C, self.dev, self.stream = C, dev, stream
-        self.host_init(oracle, pb, seed, density)
+        self.host_init(oracle, pb, seed, density, ppc, src_pages)
         with C._on_stream(stream):
             self.d_pool = to_dev(self.host, dev)
             self.crcs = to_dev(i32(self.stored), dev)
@@ -109,16 +109,16 @@ class Rig:
             self.clone.clone_slot.copy_(to_dev(i32(self.slots), dev))
             self.clone.bitmap.copy_(to_dev(i32(self.bm), dev))
 
-    def host_init(self, oracle, pb, seed, density):
+    def host_init(self, oracle, pb, seed, density, ppc=PPC, src_pages=SRC_PAGES):
         self.oracle, self.pb = oracle, pb
-        self.cb = PPC * pb
+        self.cb = ppc * pb
         self.slots = np.array(SLOTS, np.uint32)
         rng = np.random.default_rng(seed)
         self.rng = rng
         self.host = rng.integers(0, 256, N_CHUNKS * self.cb, dtype=np.uint8)
         self.stored = oracle.page_crcs(self.host, pb)
-        self.bm = random_bitmaps(rng, density)
-        self.src = rng.integers(0, 256, SRC_PAGES * pb, dtype=np.uint8)
+        self.bm = random_bitmaps(rng, density, ppc)
+        self.src = rng.integers(0, 256, src_pages * pb, dtype=np.uint8)
         self.total = 0
 
     def crc_fn(self, b):

@@ -42,11 +42,11 @@ def sync(rig):
         torch.cuda.synchronize()
 
 
-def filled_rig(dev, oracle, pb, seed, batches=(60,), stream=None, delta=False):
+def filled_rig(dev, oracle, pb, seed, batches=(60,), stream=None, delta=False, ppc=PPC):
     """A Rig after real COW batches, checked, with the four preset slot pages
     (which hold the sentinel bytes) given the CRC of those bytes, on the device
     and in the model: a clean rig reads back with no mismatch anywhere."""
-    rig = Rig(dev, oracle, pb, seed=seed, stream=stream)
+    rig = Rig(dev, oracle, pb, ppc=ppc, seed=seed, stream=stream)
     rng = np.random.default_rng(seed * 31 + pb)
     for n in batches:
         rig.batch(*random_log(rng, n, rig.orig.size, pb, pb), pb, delta)
